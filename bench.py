@@ -12,7 +12,14 @@ over the ranks exactly like the training driver does (parallel.shard_indices).  
     python bench.py --gpus 8 ...            (re-launches itself under torch.distributed.run, one rank per GPU)
     python -m torch.distributed.run --nproc-per-node 8 ... bench.py --gpus 8 --steps K --warmup W
 
-Extra objects in the JSON line:
+A plain run sets up, warms up, times --steps steps and prints the headline line.  --dump-outputs DIR also writes what the last
+timed step computed (loss, loss parts, the batch's pair ids, the updated weights) as DIR/<name>.npy: the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.  --full adds everything else (it runs more steps, kernels and
+processes after the timed region):
+
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
+
+Extra objects in the JSON line (--full):
   roofline          fused loss kernel at an HBM-saturating launch (--loss-batch pairs, working set
                     well beyond the 256 MB Infinity Cache), HIP events on the launch stream
   roofline_in_step  the same kernel as launched inside the timed steps (B = 4: 13.8 MB, cache
@@ -20,6 +27,8 @@ Extra objects in the JSON line:
   roofline_conv     the convolutions of the step against the matrix-core roof: algorithmic conv flops of the step (forward +
                     input gradient + weight gradient = 3 x forward) / the measured step time
   cpu_baseline      the reference step restated on the host CPU (oracle/cpu_step.py), rank 0, N=1 (mc only)
+  config5           BASELINE configs[4] (midas2, 384x384, BS8) as a short side run in its own process, N=1 (mc only)
+  config.host_ms_per_step, config.dp_exchange_ms   host time of one step with the GPU idle; all-reduce time per step (N > 1)
 
     python bench.py --model midas2 --height 384 --width 384 --batch-size 8      BASELINE configs[4] shape on one GPU
 """
@@ -115,6 +124,54 @@ def usable_cores() -> int:
     return max(1, n)
 
 
+def synthetic_clip_arrays(n_frames, H, W, seed=0, max_pairs=None, threads=1, flow_ops=("hierarchical2",)):
+    """The host arrays of PairStore.synthetic(n_frames, H, W, seed=seed, max_pairs=max_pairs), bit for bit: make_video +
+    video_pair_data of consistent_depth_amd/synthetic.py with their deterministic numpy work (depth rendering, reprojection flows,
+    masks) spread over `threads` threads.  The random draws stay on this thread, in the order of the sequential code, so the clip
+    does not depend on the thread count (tests/test_host_logic_cpu.py).  Returns (color, flows, masks, intrinsics, extrinsics,
+    pairs, gt_depth)."""
+    from collections import deque
+    from concurrent.futures import ThreadPoolExecutor
+    from consistent_depth_amd import synthetic as syn
+    from consistent_depth_amd.utils import frame_range as fr, frame_sampling as fs
+    noise_px, mask_keep = 0.5, 0.7                                      # video_pair_data's defaults
+    rng = np.random.default_rng(seed)                                   # make_video
+    K = syn.clip_intrinsics(H, W)
+    extr = syn.camera_path(n_frames, rng, step=0.01, max_angle=0.15)
+    surf = syn.Surface(rng)
+    intr = np.tile(K, (n_frames, 1))
+    pairs = sorted(fs.SamplePairs.to_one_way(fs.sample_pairs(fr.FrameRange(fr.OptionalSet(), n_frames), flow_ops)))
+    if max_pairs:
+        pairs = pairs[:max_pairs]
+    flows = np.empty((len(pairs), 2, 2, H, W), np.float32)
+    masks = np.empty((len(pairs), 2, 1, H, W), np.float32)
+    yy, xx = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+
+    def pair_dir(p, d, a, b, noise, keep):
+        f = syn.reprojection_flow(depth[a], intr[a], extr[a], intr[b], extr[b])
+        f = f + noise
+        inb = ((xx + f[0] >= 0) & (xx + f[0] <= W - 1) & (yy + f[1] >= 0) & (yy + f[1] <= H - 1))
+        flows[p, d] = f.astype(np.float32)
+        masks[p, d] = ((keep < mask_keep) & inb).astype(np.float32)[None]
+
+    with ThreadPoolExecutor(max(1, threads)) as ex:
+        depth_jobs = [ex.submit(syn.render_depth, surf, K, extr[i], H, W) for i in range(n_frames)]
+        color = rng.random((n_frames, 3, H, W), dtype=np.float32)
+        depth = np.stack([j.result() for j in depth_jobs])
+        rng = np.random.default_rng(seed + 1)                           # PairStore.synthetic's pair stream
+        pending = deque()
+        for p, (i, j) in enumerate(pairs):
+            for d, (a, b) in enumerate(((i, j), (j, i))):
+                noise = rng.normal(0, noise_px, (2, H, W))
+                keep = rng.random((H, W))
+                pending.append(ex.submit(pair_dir, p, d, a, b, noise, keep))
+                while len(pending) > 8 * max(1, threads):              # bounds the random planes held in flight
+                    pending.popleft().result()
+        while pending:
+            pending.popleft().result()
+    return color, flows, masks, intr, extr, pairs, depth
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -154,6 +211,16 @@ def parse():
     ap.add_argument("--cpu-timeout", type=int, default=240, help="seconds the CPU-baseline subprocess may take")
     ap.add_argument("--miopen-find", action="store_true",
                     help="torch backend only: let MIOpen benchmark-search every conv (minutes of start-up)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements and checks after the headline: host time per step, the in-step loss kernel timing, "
+                         "roofline / roofline_in_step / roofline_conv, the all-reduce timer (N > 1), cpu_baseline and config5 (the --no-* "
+                         "options above switch single ones off).  Without it a run sets up, warms up, times --steps steps, writes "
+                         "--dump-outputs and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy (rank 0): loss.npy, one "
+                         "file per loss part, pair_ids.npy (the batch of that step) and params.npy (the network weights after its Adam "
+                         "update; a fixed sample of them, indices in params_index.npy, where all of them would exceed %d MB)"
+                         % (DUMP_PARAM_BYTES >> 20))
     return ap.parse_args()
 
 
@@ -200,6 +267,27 @@ def profile_collect(lib, cap):
 
 
 LOSS_WARM_CALLS = 100
+DUMP_PARAM_BYTES = 48 << 20   # params.npy: all weights up to this size (mc: 21 MB), a fixed seeded sample of this size beyond (midas2)
+
+
+def dump_outputs(out_dir, loss, parts, pair_ids, flat_param):
+    """What the last timed step computed, as float32 / float64 .npy files (see --dump-outputs)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss.detach().reshape(-1).float().cpu().numpy(),
+              "pair_ids": pair_ids.detach().cpu().numpy().astype(np.float64)}
+    for k, v in parts.items():
+        if torch.is_tensor(v):
+            arrays[f"part_{k}"] = v.detach().float().cpu().numpy()
+    n = flat_param.numel()
+    if 4 * n > DUMP_PARAM_BYTES:      # weight + float64 index per sampled entry
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_PARAM_BYTES // 12, replace=False))
+        arrays["params"] = flat_param[torch.as_tensor(idx, device=flat_param.device)].cpu().numpy()
+        arrays["params_index"] = idx.astype(np.float64)
+    else:
+        arrays["params"] = flat_param.detach().cpu().numpy()
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(a))
+    return sorted(arrays)
 
 
 def midas_path_note():
@@ -277,6 +365,36 @@ def loss_traffic_pmc(B, H, W, timeout, kernel_substr="loss_sweep_kernel"):
     return 2.0 * got["FETCH_SIZE"] + got["WRITE_SIZE"], "rocprofv3 --pmc, separate passes, this run: 2 x FETCH_SIZE (gfx950 correction) + WRITE_SIZE, KiB -> bytes"
 
 
+def full_in_run_measurements(args, lib, step, eager_step, store, plans, device, world, graphed):
+    """--full, every rank, after the timed region: host time per step and the in-step loss kernel timing.  Both run more steps."""
+    import torch.distributed as dist
+    # What the HOST does per step, measured with the GPU idle at the start of each step (5 extra steps, every rank): main()'s t_enqueue is the
+    # wall time of the free-running loop, in which hipGraphLaunch blocks while the previous replay of the same graph is still executing
+    # (round 6, tools/host_cost.py: 11.3 ms/step free-running vs 1.3-1.4 ms/step of actual host work on both clips).
+    host_idle = []
+    for _ in range(5):
+        torch.cuda.synchronize()
+        th = time.perf_counter()
+        step.step_from_store(store, plans.next())
+        host_idle.append(time.perf_counter() - th)
+    torch.cuda.synchronize()
+    # With graph replay the in-step loss kernel is timed in 3 eager steps after the timed region.  Those steps contain the
+    # gradient all-reduce, so the decision to run them must be the same on every rank (capture could fail on a single one).
+    extra = graphed
+    if world > 1:
+        flag = torch.tensor([1.0 if graphed else 0.0], device=device)
+        dist.all_reduce(flag, op=dist.ReduceOp.MAX)
+        extra = flag.item() > 0
+    if extra:
+        if graphed:       # (an eager rank has had the profiler on since before the timed region)
+            assert lib.cd_profile_begin(16) == 0
+        for i in range(3):
+            eager_step.step_from_store(store, plans.next())
+        torch.cuda.synchronize()
+    ms_step, _ = profile_collect(lib, 16 if graphed else args.steps + 8)
+    return host_idle, ms_step
+
+
 def main():
     args = parse()
     from consistent_depth_amd import _native, parallel
@@ -316,7 +434,14 @@ def main():
         args.frames = 244 if world == 1 else 1000
     gen_dev = args.generator == "device" or (args.generator == "auto" and args.frames > 244)
     t_gen = time.perf_counter()
-    store = (PairStore.synthetic_device if gen_dev else PairStore.synthetic)(args.frames, H, W, seed=0, device=device, max_pairs=args.max_pairs or None)
+    if gen_dev:
+        store = PairStore.synthetic_device(args.frames, H, W, seed=0, device=device, max_pairs=args.max_pairs or None)
+    else:     # PairStore.synthetic's clip, its numpy work on the usable host cores
+        color, flows, masks, intr, extr, pairs, gt_depth = synthetic_clip_arrays(args.frames, H, W, seed=0, max_pairs=args.max_pairs or None,
+                                                                                 threads=usable_cores())
+        store = PairStore(color, flows, masks, intr, extr, [list(p) for p in pairs], device=device)
+        store.gt_depth = gt_depth
+        del color, flows, masks
     torch.cuda.synchronize()
     plans = EpochPlans(len(store), rank, world, B, device, seed=0)
     log(f"pair store: {args.frames} frames, {len(store)} pairs, {store.nbytes / 1e9:.2f} GB resident, generated on the "
@@ -338,12 +463,15 @@ def main():
         log(f"scale calibration: scene scaled by {scene_scale:.5g} to the network's initial depth")
 
     step_losses = []
+    last_step = {}
 
     def run(n):
         last = None
         for _ in range(n):
-            last, _, _ = step.step_from_store(store, plans.next())
+            ids = plans.next()
+            last, parts, _ = step.step_from_store(store, ids)
             step_losses.append(last)
+            last_step.update(loss=last, parts=parts, pair_ids=ids)
         return last
 
     for i in range(args.warmup):
@@ -364,11 +492,12 @@ def main():
     graphed = bool(args.graph) and getattr(step, "graphed", None) is True
     if args.graph and not graphed:
         log(f"HIP graph capture not active ({getattr(step, 'capture_error', None) or 'needs >= 3 warm-up steps'}); eager steps")
-    if not graphed:   # event records of the in-step loss profiler are not captured into graphs: eager only
+    if args.full and not graphed:   # event records of the in-step loss profiler are not captured into graphs: eager only
         assert lib.cd_profile_begin(args.steps + 8) == 0
     from consistent_depth_amd import parallel as _par
-    if world > 1:     # HIP events around every step's gradient all-reduce: the first real multi-GPU run diagnoses itself
+    if args.full and world > 1:     # HIP events around every step's gradient all-reduce: the first real multi-GPU run diagnoses itself
         _par.exchange_timer.start(args.steps)
+    if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -380,7 +509,7 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    exchange_ms = _par.exchange_timer.stop() if world > 1 else []
+    exchange_ms = _par.exchange_timer.stop() if args.full and world > 1 else []
     # A non-finite loss makes the device-side guard skip the Adam update of that step (the reference skips NaN steps too,
     # depth_fine_tuning.py:372-376): such a step is not a full step, and a timed region containing one is not a measurement.
     # (graph replays return a clone of the static loss buffer: one tensor per step here too)
@@ -391,42 +520,18 @@ def main():
     if finite_steps != args.steps:
         sys.exit(f"bench.py: {args.steps - finite_steps} of {args.steps} timed steps had a non-finite loss (Adam update skipped): "
                  f"not a valid measurement")
-    # What the HOST does per step, measured with the GPU idle at the start of each step (5 extra steps, every rank): t_enqueue above is the
-    # wall time of the free-running loop, in which hipGraphLaunch blocks while the previous replay of the same graph is still executing
-    # (round 6, tools/host_cost.py: 11.3 ms/step free-running vs 1.3-1.4 ms/step of actual host work on both clips).
-    host_idle = []
-    for _ in range(5):
-        torch.cuda.synchronize()
-        th = time.perf_counter()
-        step.step_from_store(store, plans.next())
-        host_idle.append(time.perf_counter() - th)
-    torch.cuda.synchronize()
-    # With graph replay the in-step loss kernel is timed in 3 eager steps after the timed region.  Those steps contain the
-    # gradient all-reduce, so the decision to run them must be the same on every rank (capture could fail on a single one).
-    extra = graphed
-    if world > 1:
-        flag = torch.tensor([1.0 if graphed else 0.0], device=device)
-        dist.all_reduce(flag, op=dist.ReduceOp.MAX)
-        extra = flag.item() > 0
-    if extra:
-        if graphed:       # (an eager rank has had the profiler on since before the timed region)
-            assert lib.cd_profile_begin(16) == 0
-        for i in range(3):
-            eager_step.step_from_store(store, plans.next())
-        torch.cuda.synchronize()
-    ms_step, _ = profile_collect(lib, 16 if graphed else args.steps + 8)
+    if args.dump_outputs and rank == 0:      # before anything below runs another step
+        names = dump_outputs(args.dump_outputs, last_step["loss"], last_step["parts"], last_step["pair_ids"], eager_step.opt.flat_param)
+        log(f"outputs of the last timed step written to {args.dump_outputs}: {', '.join(names)}")
     if world > 1:
         te = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
         elapsed = te.item()
     pairs_per_s = B * world * args.steps / elapsed
-    if args.model == "mc":
-        macs_per_image = mc_conv_macs(H, W)
-    else:
-        macs_per_image = module_conv_macs(model.model, torch.zeros(1, 3, H, W, device=device))
     log(f"timed region: {args.steps} steps in {elapsed:.3f}s -> {pairs_per_s:.2f} pairs/s "
         f"(free-running host loop {1e3 * t_enqueue / args.steps:.1f} ms/step)")
-
+    if args.full:
+        side = full_in_run_measurements(args, lib, step, eager_step, store, plans, device, world, graphed)
     out = {
         "metric": "frame-pairs/sec fine-tuning @384x224 BS4; warp+loss HBM GB/s vs peak",
         "value": round(pairs_per_s, 3), "unit": "frame-pairs/s", "n_gpus": world, "steps": args.steps,
@@ -465,15 +570,21 @@ def main():
                        "dp_exchange_ms": ({"mean": round(float(np.mean(exchange_ms)), 4), "min": round(float(np.min(exchange_ms)), 4),
                                            "max": round(float(np.max(exchange_ms)), 4), "steps": len(exchange_ms)} if exchange_ms else None)}
                       if world > 1 else {}),
-                   "host_ms_per_step": round(1e3 * float(np.median(host_idle)), 3),
-                   "host_ms_per_step_note": "host time of one step (gather launch + graph replay + bookkeeping) with the GPU idle at its start, median of 5 extra steps",
+                   **({"host_ms_per_step": round(1e3 * float(np.median(side[0])), 3),
+                       "host_ms_per_step_note": "host time of one step (gather launch + graph replay + bookkeeping) with the GPU idle at its start, median of 5 extra steps"}
+                      if args.full else {}),
                    "host_loop_ms_per_step": round(1e3 * t_enqueue / args.steps, 2),
                    "host_loop_note": "wall time of the free-running timed loop per step: includes hipGraphLaunch blocking while the previous replay runs (not host work)",
                    "last_loss": float(last_loss.item()), "finite_loss_steps": finite_steps,
                    **({"scene_scale": round(scene_scale, 6)} if scene_scale != 1.0 else {})},
     }
 
-    if rank == 0:
+    if rank == 0 and args.full:
+        ms_step = side[1]
+        if args.model == "mc":
+            macs_per_image = mc_conv_macs(H, W)
+        else:
+            macs_per_image = module_conv_macs(model.model, torch.zeros(1, 3, H, W, device=device))
         px = H * W
         flops_per_pair = 2 * 3 * 2 * macs_per_image            # 2 images x (forward + input gradient + weight gradient) x 2 flop/MAC
         ach_tf = flops_per_pair * pairs_per_s / world / 1e12  # per GPU
@@ -582,7 +693,7 @@ def main():
             log("config 5 side measurement (midas2, 384x384, BS8)")
             import subprocess
             cmd = [sys.executable, os.path.abspath(__file__), "--model", "midas2", "--height", "384", "--width", "384", "--batch-size", "8",
-                   "--steps", "5", "--warmup", "2", "--frames", "20", "--no-loss-microbench", "--no-cpu-baseline", "--backend", args.backend]
+                   "--steps", "5", "--warmup", "2", "--frames", "20", "--full", "--no-loss-microbench", "--no-cpu-baseline", "--backend", args.backend]
             stderr_tail = ""
             try:
                 r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.config5_timeout)
@@ -595,6 +706,7 @@ def main():
                                   "workload": c5["config"]["workload"], "roofline_conv": c5.get("roofline_conv")}
             except (subprocess.TimeoutExpired, IndexError, ValueError, KeyError) as e:
                 out["config5"] = {"value": None, "note": f"no line within {args.config5_timeout}s ({type(e).__name__}): {stderr_tail}"}
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

@@ -2,6 +2,7 @@
 snapshot (RUNS of them, one after the other) with the hourglass convolutions on PyTorch-ROCm / MIOpen (BASELINE configs[1]) and the HIP loss / Adam.
 
     python tests/config1_worker.py <job.pt>
+    python tests/config1_worker.py --warm          (started by tests/conftest.py: see warm())
 
 job.pt (torch.save): snap (state / m1 / m2 / k, CPU tensors), clip (make_synthetic_dataset arguments), paths (one per run), K, T, n_pairs, plans
 ({epoch: [[pair, ...], ...]}), pair_order.  Writes every run's artefacts under its path's output directory and prints one OUT_DIR= line per finished run.
@@ -44,5 +45,31 @@ def main():
         del ft
         torch.cuda.empty_cache()
 
+def warm():
+    """MIOpen compiles the kernels of every convolution problem on first use and keeps them in the user's cache: on an empty cache
+    the test's first continuation spends ~150 s compiling.  One epoch of the same fine-tuner on the same clip (fresh weights: only
+    the problems matter) in a background process started at collection fills the cache while the other tests run."""
+    import tempfile
+    import torch
+    os.environ["CD_AMD_MC_BACKEND"] = "torch"
+    torch.backends.cudnn.benchmark = False
+    import make_synthetic_dataset as msd
+    from consistent_depth_amd.depth_fine_tuning import DepthFineTuner
+    from consistent_depth_amd.params import Video3dParamsParser
+    from oracle import gen_golden_loop_384 as G
+    clip = G.SPECS["a"]["clip"]
+    with tempfile.TemporaryDirectory(prefix="cd_miopen_warm_") as td:
+        path = os.path.join(td, "clip")
+        range_dir, _ = msd.write_dataset(path, **clip)
+        params = Video3dParamsParser().parse(["--path", path, "--num_epochs", "1", "--batch_size", "4", "--print_freq", "0"])
+        ft = DepthFineTuner(range_dir, list(range(clip["n_frames"])), params)
+        assert ft.model.backend == "torch"
+        ft.fine_tune()
+        torch.cuda.synchronize()
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["--warm"]:
+        warm()
+    else:
+        main()

@@ -168,7 +168,10 @@ def pytest_collection_finish(session):
     as it is known that the test will run, so that it overlaps with the other GPU tests."""
     import subprocess
     import tempfile
-    if os.environ.get("CD_AMD_TEST_NO_BG") or not any("baseline_8x384x224" in it.nodeid for it in session.items):
+    if os.environ.get("CD_AMD_TEST_NO_BG"):
+        return
+    start_miopen_warmup(session.items)
+    if not any("baseline_8x384x224" in it.nodeid for it in session.items):
         return
     if not os.environ.get("CD_AMD_TEST_LIVE_ENGINE_REF"):
         import bg_reference
@@ -181,6 +184,31 @@ def pytest_collection_finish(session):
     proc = subprocess.Popen([sys.executable, os.path.join(REPO, "tests", "bg_reference.py"), dst, str(threads)],
                             stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, env={**os.environ, "HIP_VISIBLE_DEVICES": ""})
     _BG["engine_ref"] = (proc, dst)
+
+
+def start_miopen_warmup(items):
+    """The configs[1] test (run last) compiles MIOpen's kernels into the user's cache on its first continuation: on an empty cache
+    (a fresh home) that took it from ~75 s to 221 s.  tests/config1_worker.py --warm fills the cache in the background while the
+    other GPU tests run; the test waits for it (wait_miopen_warmup) before its own runs."""
+    import subprocess
+    if len(items) < 20 or not any(it.nodeid.endswith(_THIRD_PARTY_LAST) for it in items):
+        return
+    proc = subprocess.Popen([sys.executable, os.path.join(REPO, "tests", "config1_worker.py"), "--warm"], stdout=subprocess.DEVNULL,
+                            stderr=subprocess.DEVNULL, env={**os.environ, "CD_AMD_MC_BACKEND": "torch"})
+    _BG["miopen_warm"] = (proc, None)
+
+
+def wait_miopen_warmup(timeout=400):
+    """Wait for the background MIOpen warm-up, if one was started.  Its outcome does not matter: the test's runs compile whatever
+    the cache lacks."""
+    if "miopen_warm" not in _BG:
+        return None
+    proc, _ = _BG["miopen_warm"]
+    try:
+        return proc.wait(timeout=timeout)
+    except Exception:   # noqa: BLE001
+        proc.kill()
+        return None
 
 
 def pytest_sessionfinish(session, exitstatus):

@@ -66,9 +66,9 @@ def test_conv_fwd_matches_torch(N, Cin, Cout, H, W, ks, ty):
                                                (1, 64, 64, 96, 56, 11)])
 def test_split_arithmetic_is_as_close_to_fp64_as_the_fp32_instruction(N, Cin, Cout, H, W, ks, arith):
     """The licence for the split-bf16 kernel: on the same inputs its distance to the fp64 result is not larger than that of
-    the fp32 matrix instruction (both printed).  Inputs with a non-zero mean (post-ReLU activations) make the sums long."""
-    if arith != "split":
-        pytest.skip("one comparison covers both modes")
+    the fp32 matrix instruction (both printed).  Inputs with a non-zero mean (post-ReLU activations) make the sums long.  The comparison
+    sets both modes itself; in addition, under "split3" the k x k result is the split kernel's bit for bit (the same kernels), and under
+    "fp32" the instruction stays within the fp32 bound of test_conv_fwd_matches_torch on these long sums."""
     import torch
     from consistent_depth_amd import _native
     from consistent_depth_amd.ops import conv
@@ -84,6 +84,15 @@ def test_split_arithmetic_is_as_close_to_fp64_as_the_fp32_instruction(N, Cin, Co
         y = conv.conv2d(x.cuda(), pk, Cin, Cout, ks)
         d = (y.cpu().double() - ref).abs()
         err[name] = (d.max().item() / ref.abs().max().item(), (d.pow(2).mean().sqrt() / ref.pow(2).mean().sqrt()).item())
+        if name == "split":
+            y_split = y
+    if arith == "split3":
+        lib.cd_set_conv_arith(1)
+        assert torch.equal(conv.conv2d(x.cuda(), pk, Cin, Cout, ks), y_split)
+    if arith == "fp32":
+        assert err["fp32"][0] < 2e-5, err["fp32"]
+    if arith != "split":
+        return
     report("conv_split_vs_fp32", shape=f"{N}x{Cin}->{Cout}x{H}x{W}k{ks}", split_max=f"{err['split'][0]:.2e}", fp32_max=f"{err['fp32'][0]:.2e}",
            split_rms=f"{err['split'][1]:.2e}", fp32_rms=f"{err['fp32'][1]:.2e}")
     assert err["split"][0] <= 1.5 * err["fp32"][0] + 1e-8 and err["split"][1] <= 1.25 * err["fp32"][1] + 1e-9
@@ -381,8 +390,6 @@ def test_branches_of_an_inception_in_one_dispatch(arith, N, H, W, cin, cout, kss
     import torch
     from consistent_depth_amd import _native
     from consistent_depth_amd.ops import conv
-    if cfg[0] == 32 and (arith == "fp32" or cout <= 16):
-        pytest.skip("launch shape 32 (8 row tiles + two chunks per round): split-bf16 kernels with 32 output channels per column tile only")
     g = torch.Generator(device="cuda").manual_seed(11)
     nb = len(kss)
     P = torch.randn(N, nb * cin + nb * cout, H, W, device="cuda", generator=g)
@@ -394,6 +401,20 @@ def test_branches_of_an_inception_in_one_dispatch(arith, N, H, W, cin, cout, kss
         return [dict(x=P, packed_w=conv.pack_weights(w), Cin=cin, Cout=cout, ks=k, bias=b, x_coff=i * cin, out=out, y_coff=nb * cin + i * cout,
                      in_scale=sc[i * cin:(i + 1) * cin], in_shift=sh[i * cin:(i + 1) * cin], in_relu=True, stats=stats)
                 for i, (k, w, b) in enumerate(zip(kss, ws, bs))]
+    if cfg[0] == 32 and (arith == "fp32" or cout <= 16):
+        # launch shape 32 (8 row tiles + two chunks per round) exists for the split-bf16 k x k kernels with 32 output channels per column
+        # tile only: everywhere else the library refuses it, merged and one by one, before anything is launched (the tuner relies on it)
+        out = torch.zeros_like(P)
+        st = torch.zeros(_native.BN_STAT_SLOTS, P.shape[1], 2, dtype=torch.float64, device="cuda")
+        ms = members(out, st.view(-1))
+        assert conv.conv2d_multi(ms, cfg) is False
+        for m in ms:
+            with pytest.raises(RuntimeError, match="CD_ERR_UNSUPPORTED"):
+                conv.conv2d(m["x"], m["packed_w"], cin, cout, m["ks"], bias=m["bias"], x_coff=m["x_coff"], out=out, y_coff=m["y_coff"],
+                            in_scale=m["in_scale"], in_shift=m["in_shift"], in_relu=True, stats=m["stats"], cfg=cfg)
+        torch.cuda.synchronize()
+        assert not out.any() and not st.any()
+        return
     outs, stats = [], []
     for merged in (False, True):
         out = torch.zeros_like(P)

@@ -124,7 +124,63 @@ def test_bench_cli_contract():
     for flag in ("--gpus", "--steps", "--warmup"):
         assert f'"{flag}"' in src
     assert spec is not None and '"cpu_baseline"' in src and '"roofline"' in src and "higher_is_better" in src
+    for flag in ("--full", "--dump-outputs"):
+        assert f'"{flag}"' in src
     del sys
+
+
+def _bench_module():
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+@pytest.mark.parametrize("threads", [1, 4])
+def test_bench_clip_is_pair_store_synthetic_bit_for_bit(threads):
+    """bench.py builds PairStore.synthetic's clip with its numpy work on a thread pool: the arrays must be those of the sequential
+    make_video + video_pair_data calls PairStore.synthetic makes, bit for bit, whatever the thread count."""
+    import numpy as np
+    from consistent_depth_amd import synthetic as syn
+    from consistent_depth_amd.utils import frame_range as fr, frame_sampling as fs
+    n, H, W, seed = 14, 40, 24, 3
+    color, flows, masks, intr, extr, pairs, depth = _bench_module().synthetic_clip_arrays(n, H, W, seed=seed, threads=threads)
+    video = syn.make_video(n, H, W, seed)
+    rng = np.random.default_rng(seed + 1)
+    want = sorted(fs.SamplePairs.to_one_way(fs.sample_pairs(fr.FrameRange(fr.OptionalSet(), n), ("hierarchical2",))))
+    assert pairs == want and len(pairs) > n
+    for k, a in (("color", color), ("gt_depth", depth), ("intrinsics", intr), ("extrinsics", extr)):
+        assert a.dtype == video[k].dtype and np.array_equal(a, video[k]), k
+    for p, (i, j) in enumerate(pairs):
+        (f0, m0), (f1, m1) = syn.video_pair_data(video, i, j, rng)
+        assert np.array_equal(flows[p, 0], f0) and np.array_equal(flows[p, 1], f1)
+        assert np.array_equal(masks[p, 0], m0) and np.array_equal(masks[p, 1], m1)
+    assert 0 < masks.mean() < 1
+
+
+def test_bench_dump_outputs_writes_float_arrays_within_the_size_limit(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files only, at most 64 MB in all, the weights sampled the same way every time."""
+    import numpy as np
+    bench = _bench_module()
+    n = 3 * bench.DUMP_PARAM_BYTES // 4
+    flat = torch.arange(n, dtype=torch.float32)
+    parts = {"reprojection": torch.rand(4), "disparity": torch.rand(4)}
+    names = bench.dump_outputs(str(tmp_path / "a"), torch.tensor([0.5]), parts, torch.arange(4), flat)
+    bench.dump_outputs(str(tmp_path / "b"), torch.tensor([0.5]), parts, torch.arange(4), flat)
+    assert names == ["loss", "pair_ids", "params", "params_index", "part_disparity", "part_reprojection"]
+    total = 0
+    for name in names:
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), name
+        total += (tmp_path / "a" / f"{name}.npy").stat().st_size
+    assert total <= 64 << 20
+    params, index = np.load(tmp_path / "a" / "params.npy"), np.load(tmp_path / "a" / "params_index.npy")
+    assert np.array_equal(params, index.astype(np.float32)) and len(np.unique(index)) == len(index)
+    small = bench.dump_outputs(str(tmp_path / "c"), torch.tensor([0.5]), parts, torch.arange(4), flat[:1000])
+    assert "params_index" not in small and np.array_equal(np.load(tmp_path / "c" / "params.npy"), flat[:1000].numpy())
 
 
 def test_bench_flop_count_matches_the_convolutions_a_forward_pass_executes(monkeypatch):

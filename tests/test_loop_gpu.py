@@ -407,6 +407,8 @@ def test_config1_torch_convs_hip_loss_from_the_same_snapshot(tmp_path, monkeypat
     cpu = lambda d: {k: (v.detach().cpu() if torch.is_tensor(v) else v) for k, v in d.items()}  # noqa: E731
     snap_cpu = {"state": cpu(snap["state"]), "m1": cpu(snap["m1"]), "m2": cpu(snap["m2"]), "k": snap["k"]}
     worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "config1_worker.py")
+    import conftest
+    conftest.wait_miopen_warmup()        # MIOpen's kernels, compiled in the background while the other tests ran
     killed, out_dirs = 0, []
     for attempt in range(2):
         todo = RUNS - len(out_dirs)

@@ -497,12 +497,35 @@ def test_sweep_workspace_header(torch_cuda, variant):
     hand-off of the per-pair losses: 60 launches.)"""
     torch = torch_cuda
     from consistent_depth_amd import _native, synthetic
-    if variant != 4:
-        pytest.skip("the header is the row sweep's")
     lib = _native.lib()
     H, W = 64, 96
     batches = {B: to_dev(synthetic.make_scene_batch(B, H, W, seed=20 + B), torch) for B in (7, 3, 12)}
     ws = torch.full((lib.cd_consistency_loss_workspace_bytes(12, H, W),), 0x5a, dtype=torch.uint8, device="cuda")
+    if variant != 4:
+        # the header is the row sweep's: the slab formulation neither needs nor touches it.  On a workspace that was never initialised
+        # its total is the mean of the per-pair losses and the header's 256 bytes stay as they were; after
+        # cd_consistency_loss_workspace_init the header keeps what the init wrote (counter 0) and every call of the same batch size is
+        # bitwise the one on the uninitialised buffer.
+        first = {}
+        for B in (7, 3, 12):
+            out, grad = _raw_fwd_bwd(torch, batches[B], ws)
+            torch.cuda.synchronize()
+            per_pair = (out[:B].double() + out[B:2 * B].double()).mean().item()
+            assert abs(out[-1].item() - per_pair) <= 2e-7 * abs(per_pair), (B, out[-1].item(), per_pair)
+            first[B] = (out.clone(), grad.clone())
+        assert bool((ws[:256] == 0x5a).all()), ws[:8]
+        assert lib.cd_consistency_loss_workspace_init(ws.data_ptr(), ws.numel(), _native.stream_ptr(ws.device)) == 0
+        torch.cuda.synchronize()
+        hdr = ws[:256].view(torch.int32)
+        hdr0 = hdr.clone()
+        assert int(hdr0[1]) == 0
+        for it in range(12):
+            B = (7, 3, 12)[it % 3]
+            out, grad = _raw_fwd_bwd(torch, batches[B], ws)
+            torch.cuda.synchronize()
+            assert torch.equal(hdr, hdr0), (it, B, hdr[:2].tolist())
+            assert torch.equal(first[B][0], out) and torch.equal(first[B][1], grad), (it, B)
+        return
     out, _ = _raw_fwd_bwd(torch, batches[7], ws)
     torch.cuda.synchronize()
     assert torch.isnan(out[-1]), "an uninitialised workspace must not report a mean loss"
