@@ -13,7 +13,7 @@ import torch  # imported first on purpose: libcd_amd.so then binds to torch's li
 _PKG = os.path.dirname(os.path.abspath(__file__))
 # CD_AMD_LIB: load another build of the SAME library (A/B measurements of kernel variants, tools/exp/build_variants.sh); not a fallback
 SO_PATH = os.environ.get("CD_AMD_LIB") or os.path.join(_PKG, "libcd_amd.so")
-ABI_VERSION = 9
+ABI_VERSION = 10
 BN_STAT_SLOTS = 16   # CD_BN_STAT_SLOTS of include/consistent_depth_amd.h (checked by tests/test_abi.py)
 
 _lib = None
@@ -104,6 +104,12 @@ SIGNATURES = {
     "cd_adam_step_flat_guarded": (c_i, [c_p] * 4 + [c_sz, c_f, c_f, c_f, c_f, c_p, c_p, c_f, c_p]),
     "cd_l1_distance_workspace_bytes": (c_sz, [c_sz]),
     "cd_l1_distance": (c_i, [c_p, c_p, c_sz, c_p, c_p, c_sz, c_p]),
+    "cd_bicubic_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_f, c_f, c_p]),
+    "cd_bicubic_bwd": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "cd_pad_cat_fwd": (c_i, [c_p, c_i, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_p]),
+    "cd_pad_cat_bwd": (c_i, [c_p, c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_i, c_p]),
+    "cd_crop_act_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
+    "cd_crop_act_bwd": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
 }
 
 STATUS = {0: "CD_OK", -1: "CD_ERR_INVALID_ARG", -2: "CD_ERR_WORKSPACE", -3: "CD_ERR_LAUNCH", -4: "CD_ERR_UNSUPPORTED"}

@@ -49,9 +49,11 @@ typedef enum cd_depth_mode {
  * cd_conv2d_fwd_multi added, cd_bn_relu_bwd's last
  * argument became a flags bitfield, cd_debug_set_loss_variant(2) is refused;
  * 9: cd_consistency_loss_workspace_init added -- a loss workspace must be initialised once before its first use; cd_copy_segments,
- *    cd_counters_add, cd_zero_bytes, cd_debug_set_layers_mode added).
+ *    cd_counters_add, cd_zero_bytes, cd_debug_set_layers_mode added;
+ * 10: cd_bicubic_fwd / cd_bicubic_bwd / cd_pad_cat_fwd / cd_pad_cat_bwd / cd_crop_act_fwd / cd_crop_act_bwd added -- the monodepth2
+ *    decoder and its resizing).
  * The loader (consistent_depth_amd/_native.py) refuses a library whose cd_abi_version() differs from this constant. */
-#define CD_ABI_VERSION 9
+#define CD_ABI_VERSION 10
 int cd_abi_version(void);
 
 /* Batch-statistics buffers (the `stats` arguments below) hold CD_BN_STAT_SLOTS partial copies:
@@ -529,6 +531,28 @@ int cd_zero_bytes(void* p, size_t bytes, void* stream);
 /* out[c] (+)= sum over n,y,x of src[n][coff+c]  -- bias gradient of a conv not followed by BatchNorm. */
 int cd_channel_sum(const float* src, int ctot, int coff, int C, int N, int H, int W, float* out,
                    int accumulate, void* stream);
+
+/* ---- monodepth2 (KITTI preset; reference: monodepth/monodepth2_model.py:61-91 and the un-vendored DepthDecoder).  (ABI 10)
+ * All tensors fp32 NCHW, contiguous; no atomics (every backward is a gather in a fixed order: bit-reproducible).
+ * cd_bicubic_fwd: y (NC, Hout, Wout) = F.interpolate(x (NC, Hin, Win), size=(Hout, Wout), mode="bicubic", align_corners=False), then
+ *   (y - sub) / div if norm != 0.  ytab / xtab: per output index of each axis {int idx[4]; float w[4]} (32 bytes; source indices
+ *   already clamped to [0, in-1]), built on the host (consistent_depth_amd/ops/resample.py).  NC <= 65535.
+ * cd_bicubic_bwd: dx (NC, Hin, Win) = Wy^T dy Wx as two gathers over inverted tables: for input index i the entries
+ *   off[i] .. off[i+1]-1 of {int o; float w;} (fixed order).  tmp: NC * Hout * Win floats of scratch.
+ * cd_pad_cat_fwd: out (N, C1+C2, H+2, W+2) = reflect_pad1(cat(up(x), skip)), x (N, C1, H/up, W/up), up = 1 (identity) or 2 (nearest x2,
+ *   src = dst / 2), skip (N, C2, H, W) or NULL with C2 = 0.  H, W >= 2.
+ * cd_pad_cat_bwd: the adjoint: dx (N, C1, H/up, W/up) and dskip (N, C2, H, W) (NULL with C2 = 0), assigned.
+ * cd_crop_act_fwd: y (NC, H, W) = act(in[:, 1:-1, 1:-1]), in (NC, H+2, W+2); act 0 = ELU(alpha 1), 1 = sigmoid.
+ * cd_crop_act_bwd: din (NC, H+2, W+2) = act'(y) * dy on the interior (ELU: y <= 0 ? dy * (y + 1) : dy; sigmoid: dy * y (1 - y)) and
+ *   0 on the ring -- every element written, so the buffer needs no clearing. */
+int cd_bicubic_fwd(const float* x, float* y, int NC, int Hin, int Win, int Hout, int Wout, const void* ytab, const void* xtab, int norm,
+                   float sub, float div, void* stream);
+int cd_bicubic_bwd(const float* dy, float* dx, float* tmp, int NC, int Hin, int Win, int Hout, int Wout, const int* yoff,
+                   const void* yent, const int* xoff, const void* xent, void* stream);
+int cd_pad_cat_fwd(const float* x, int C1, int up, const float* skip, int C2, float* out, int N, int H, int W, void* stream);
+int cd_pad_cat_bwd(const float* dout, float* dx, int C1, int up, float* dskip, int C2, int N, int H, int W, void* stream);
+int cd_crop_act_fwd(const float* in, float* y, int act, int NC, int H, int W, void* stream);
+int cd_crop_act_bwd(const float* dy, const float* y, float* din, int act, int NC, int H, int W, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Optimiser (reference: optimizer/__init__.py:16-17 -> torch.optim.Adam,

@@ -1,0 +1,451 @@
+"""The `monodepth2` plugin (the model of `--configure kitti`) on the GPU: the new kernels of csrc/resample.hip against fp64 ATen, the
+whole network against an fp64 twin built from the ATen modules, the fine-tuning step eager and graphed, upstream-format weights, the
+absence of framework kernels from the step, and the CLI end to end."""
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import REPO
+from tests.gpu_util import report
+
+pytestmark = [pytest.mark.gpu]
+
+
+def _rel(a, b):
+    a, b = a.detach().double().cpu(), b.detach().double().cpu()
+    return float((a - b).abs().max() / max(float(b.abs().max()), 1e-300))
+
+
+# ------------------------------------------------------------------------------------------------------------------ kernels
+@pytest.mark.parametrize("case", [((8, 3, 224, 384), (320, 1024), True), ((8, 1, 320, 1024), (224, 384), False),
+                                  ((2, 3, 64, 48), (320, 1024), True), ((2, 1, 320, 1024), (64, 48), False)],
+                         ids=["frame_to_feed", "feed_to_frame", "small_to_feed", "feed_to_small"])
+def test_bicubic_matches_aten_fp64(case):
+    import torch
+    import torch.nn.functional as F
+    from consistent_depth_amd.ops.resample import bicubic_resize
+    shape, size, norm = case
+    g = torch.Generator().manual_seed(shape[1] * 1000 + size[0])
+    x64 = torch.rand(shape, dtype=torch.float64, generator=g)
+    xg = x64.float().cuda().requires_grad_(True)
+    y = bicubic_resize(xg, size, norm=(0.45, 0.225) if norm else None)
+    xd = x64.clone().requires_grad_(True)
+    yd = F.interpolate(xd, size=size, mode="bicubic", align_corners=False)
+    x32 = x64.float().cuda().requires_grad_(True)
+    y32 = F.interpolate(x32, size=size, mode="bicubic", align_corners=False)
+    if norm:
+        yd, y32 = (yd - 0.45) / 0.225, (y32 - 0.45) / 0.225
+    dy = torch.randn(yd.shape, dtype=torch.float64, generator=g)
+    yd.backward(dy)
+    y32.backward(dy.float().cuda())
+    dx1 = torch.autograd.grad(y, xg, dy.float().cuda(), retain_graph=True)[0]
+    dx2 = torch.autograd.grad(y, xg, dy.float().cuda())[0]
+    assert torch.equal(dx1, dx2)          # no atomics: the adjoint is bit-reproducible
+    got = {"y": _rel(y, yd), "dx": _rel(dx1, xd.grad)}
+    ref = {"y": _rel(y32, yd), "dx": _rel(x32.grad, xd.grad)}
+    report("monodepth2_bicubic", case=f"{shape}->{size}", **{k: f"{v:.2e}" for k, v in got.items()},
+           **{"ref_" + k: f"{v:.2e}" for k, v in ref.items()})
+    for k, v in got.items():
+        assert v <= max(4 * ref[k], 2e-6), (k, v, ref[k])
+
+
+@pytest.mark.parametrize("case", [(2, 8, 4, 6, 10, 1), (2, 8, 4, 6, 10, 2), (3, 5, 0, 7, 9, 1), (3, 5, 0, 7, 9, 2), (1, 3, 6, 1, 1, 2),
+                                  (2, 16, 0, 2, 6, 1)], ids=lambda c: "x".join(map(str, c)))
+def test_pad_cat_matches_aten(case):
+    """case = (N, C1, C2, h, w, up): x (N, C1, h, w), skip (N, C2, up h, up w) or none; odd extents and 2 x 2 planes included."""
+    import torch
+    import torch.nn.functional as F
+    from consistent_depth_amd import _native
+    from consistent_depth_amd.ops.resample import pad_cat
+    N, C1, C2, h, w, up = case
+    H, W = h * up, w * up
+    g = torch.Generator().manual_seed(sum(case))
+    x64 = torch.randn(N, C1, h, w, dtype=torch.float64, generator=g)
+    s64 = torch.randn(N, C2, H, W, dtype=torch.float64, generator=g) if C2 else None
+
+    def twin(x, s):
+        u = F.interpolate(x, scale_factor=2, mode="nearest") if up == 2 else x
+        return F.pad(torch.cat([u, s], 1) if s is not None else u, (1, 1, 1, 1), mode="reflect")
+
+    xg = x64.float().cuda().requires_grad_(True)
+    sg = s64.float().cuda().requires_grad_(True) if C2 else None
+    out = pad_cat(xg, up, sg)
+    assert torch.equal(out, twin(x64.float().cuda(), s64.float().cuda() if C2 else None))      # a pure copy: bit-identical
+    # every element written: the raw entry point into a NaN-filled buffer
+    raw = torch.full_like(out, float("nan"))
+    _native.check(_native.lib().cd_pad_cat_fwd(xg.data_ptr(), C1, up, sg.data_ptr() if C2 else None, C2, raw.data_ptr(), N, H, W,
+                                               _native.stream_ptr()), "cd_pad_cat_fwd")
+    assert torch.equal(raw, out)
+    dout = torch.randn(out.shape, dtype=torch.float64, generator=g)
+    xd = x64.clone().requires_grad_(True)
+    sd = s64.clone().requires_grad_(True) if C2 else None
+    twin(xd, sd).backward(dout)
+    x32 = x64.float().cuda().requires_grad_(True)
+    s32 = s64.float().cuda().requires_grad_(True) if C2 else None
+    twin(x32, s32).backward(dout.float().cuda())
+    ins = (xg, sg) if C2 else (xg,)
+    g1 = torch.autograd.grad(out, ins, dout.float().cuda(), retain_graph=True)
+    g2 = torch.autograd.grad(out, ins, dout.float().cuda())
+    assert all(torch.equal(a, b) for a, b in zip(g1, g2))
+    got = {"dx": _rel(g1[0], xd.grad)}
+    ref = {"dx": _rel(x32.grad, xd.grad)}
+    if C2:
+        got["dskip"], ref["dskip"] = _rel(g1[1], sd.grad), _rel(s32.grad, sd.grad)
+    report("monodepth2_pad_cat", case="x".join(map(str, case)), **{k: f"{v:.2e}" for k, v in got.items()})
+    for k, v in got.items():
+        assert v <= max(4 * ref[k], 2e-6), (k, v, ref[k])
+
+
+@pytest.mark.parametrize("act", ["elu", "sigmoid"])
+@pytest.mark.parametrize("shape", [(2, 16, 12, 20), (3, 5, 7, 9), (2, 1, 320, 1024)], ids=lambda s: "x".join(map(str, s)))
+def test_crop_act_matches_aten(shape, act):
+    """shape = the cropped (N, C, H, W); the input is (N, C, H + 2, W + 2).  Output buffers are NaN-filled before the raw calls so
+    that an element left unwritten (the backward's zero ring above all) shows."""
+    import torch
+    import torch.nn.functional as F
+    from consistent_depth_amd import _native
+    from consistent_depth_amd.ops.resample import crop_act
+    N, C, H, W = shape
+    code = {"elu": 0, "sigmoid": 1}[act]
+    fn = (lambda t: F.elu(t)) if act == "elu" else torch.sigmoid
+    g = torch.Generator().manual_seed(N * C + H + code)
+    xp64 = 2 * torch.randn(N, C, H + 2, W + 2, dtype=torch.float64, generator=g)
+    dy64 = torch.randn(N, C, H, W, dtype=torch.float64, generator=g)
+    xg = xp64.float().cuda()
+    lib, st = _native.lib(), _native.stream_ptr()
+    y = torch.full((N, C, H, W), float("nan"), device="cuda")
+    _native.check(lib.cd_crop_act_fwd(xg.data_ptr(), y.data_ptr(), code, N * C, H, W, st), "cd_crop_act_fwd")
+    dy = dy64.float().cuda()
+    dxs = []
+    for _ in range(2):
+        dx = torch.full((N, C, H + 2, W + 2), float("nan"), device="cuda")
+        _native.check(lib.cd_crop_act_bwd(dy.data_ptr(), y.data_ptr(), dx.data_ptr(), code, N * C, H, W, st), "cd_crop_act_bwd")
+        dxs.append(dx)
+    assert torch.equal(dxs[0], dxs[1]) and torch.isfinite(dxs[0]).all()
+    ring = dxs[0].clone()
+    ring[:, :, 1:-1, 1:-1] = 0
+    assert not ring.any()
+    # the autograd face gives the same
+    xa = xg.clone().requires_grad_(True)
+    ya = crop_act(xa, act)
+    ya.backward(dy)
+    assert torch.equal(ya, y) and torch.equal(xa.grad, dxs[0])
+    xd = xp64.clone().requires_grad_(True)
+    yd = fn(xd[:, :, 1:-1, 1:-1])
+    yd.backward(dy64)
+    x32 = xg.clone().requires_grad_(True)
+    y32 = fn(x32[:, :, 1:-1, 1:-1])
+    y32.backward(dy)
+    got = {"y": _rel(y, yd), "dx": _rel(dxs[0], xd.grad)}
+    ref = {"y": _rel(y32, yd), "dx": _rel(x32.grad, xd.grad)}
+    report("monodepth2_crop_act", case=f"{act} {shape}", **{k: f"{v:.2e}" for k, v in got.items()},
+           **{"ref_" + k: f"{v:.2e}" for k, v in ref.items()})
+    for k, v in got.items():
+        assert v <= max(4 * ref[k], 2e-6), (k, v, ref[k])
+
+
+# ------------------------------------------------------------------------------------------------------------------ fp64 twin
+def _twin(feed):
+    """Upstream's ResnetEncoder(18) + DepthDecoder from the ATen modules (nn.Conv2d, BatchNorm2d, ReflectionPad2d, ELU, F.interpolate) and
+    monodepth2_model.estimate_depth's steps up to the disparity at frame size."""
+    import torch
+    import torch.nn as nn
+    import torch.nn.functional as F
+
+    class Block(nn.Module):
+        def __init__(self, cin, p, s):
+            super().__init__()
+            self.conv1, self.bn1 = nn.Conv2d(cin, p, 3, s, 1, bias=False), nn.BatchNorm2d(p)
+            self.conv2, self.bn2 = nn.Conv2d(p, p, 3, 1, 1, bias=False), nn.BatchNorm2d(p)
+            self.downsample = nn.Sequential(nn.Conv2d(cin, p, 1, s, bias=False), nn.BatchNorm2d(p)) if (s != 1 or cin != p) else None
+
+        def forward(self, x):
+            idt = x if self.downsample is None else self.downsample(x)
+            return F.relu(self.bn2(self.conv2(F.relu(self.bn1(self.conv1(x))))) + idt)
+
+    class ResNet(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.conv1, self.bn1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False), nn.BatchNorm2d(64)
+            cin = 64
+            for i, (p, s) in enumerate(((64, 1), (128, 2), (256, 2), (512, 2)), start=1):
+                setattr(self, f"layer{i}", nn.Sequential(Block(cin, p, s), Block(p, p, 1)))
+                cin = p
+            self.fc = nn.Linear(512, 1000)
+
+    class Encoder(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.encoder = ResNet()
+
+        def forward(self, x):
+            e = self.encoder
+            f = [F.relu(e.bn1(e.conv1((x - 0.45) / 0.225)))]
+            f.append(e.layer1(F.max_pool2d(f[-1], 3, 2, 1)))
+            for layer in (e.layer2, e.layer3, e.layer4):
+                f.append(layer(f[-1]))
+            return f
+
+    class Conv3x3(nn.Module):
+        def __init__(self, cin, cout):
+            super().__init__()
+            self.pad, self.conv = nn.ReflectionPad2d(1), nn.Conv2d(cin, cout, 3)
+
+        def forward(self, x):
+            return self.conv(self.pad(x))
+
+    class ConvBlock(nn.Module):
+        def __init__(self, cin, cout):
+            super().__init__()
+            self.conv, self.nonlin = Conv3x3(cin, cout), nn.ELU(inplace=True)
+
+        def forward(self, x):
+            return self.nonlin(self.conv(x))
+
+    class Decoder(nn.Module):
+        def __init__(self):
+            super().__init__()
+            enc, dec = (64, 64, 128, 256, 512), (16, 32, 64, 128, 256)
+            convs = []
+            for i in range(4, -1, -1):
+                convs += [ConvBlock(enc[-1] if i == 4 else dec[i + 1], dec[i]), ConvBlock(dec[i] + (enc[i - 1] if i > 0 else 0), dec[i])]
+            convs += [Conv3x3(dec[s], 1) for s in range(4)]
+            self.decoder = nn.ModuleList(convs)
+
+        def forward(self, f):
+            x = f[-1]
+            for j, i in enumerate(range(4, -1, -1)):
+                x = [F.interpolate(self.decoder[2 * j](x), scale_factor=2, mode="nearest")]
+                if i > 0:
+                    x.append(f[i - 1])
+                x = self.decoder[2 * j + 1](torch.cat(x, 1))
+            return torch.sigmoid(self.decoder[10](x))
+
+    class Twin(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.encoder, self.depth_decoder = Encoder(), Decoder()
+
+        def forward(self, images):
+            H, W = images.shape[-2:]
+            x = F.interpolate(images, size=feed, mode="bicubic", align_corners=False)
+            disp = self.depth_decoder(self.encoder(x))
+            return F.interpolate(disp, size=(H, W), mode="bicubic", align_corners=False)
+
+    return Twin()
+
+
+def _compare_with_twin(hip_net, run_hip, images, feed, tag):
+    import torch
+    twins = {}
+    for name in ("rocm", "fp64"):
+        t = _twin(feed)
+        t.encoder.load_state_dict(hip_net.encoder.state_dict())
+        t.depth_decoder.load_state_dict(hip_net.depth_decoder.state_dict())
+        twins[name] = (t.cuda() if name == "rocm" else t.double()).train()
+    outs, grads = {}, {}
+    for name, run, inp in (("hip", run_hip, images.cuda()), ("rocm", twins["rocm"], images.cuda()), ("fp64", twins["fp64"], images.double())):
+        net = hip_net if name == "hip" else twins[name]
+        y = run(inp)
+        gw = torch.cos(torch.arange(y.numel(), dtype=torch.float64).reshape(y.shape) * 0.61).to(y)
+        (y * gw).sum().backward()
+        outs[name] = y.detach().double().cpu()
+        grads[name] = {k: p.grad.detach().double().cpu() for k, p in net.named_parameters() if p.grad is not None}
+    assert set(grads["hip"]) == set(grads["fp64"])
+    unused = [k for k, _ in hip_net.named_parameters() if k not in grads["fp64"]]
+    assert sorted(unused) == sorted(f"{m}.{s}" for m in ("encoder.encoder.fc", "depth_decoder.decoder.11.conv",
+                                                          "depth_decoder.decoder.12.conv", "depth_decoder.decoder.13.conv")
+                                    for s in ("weight", "bias"))
+
+    def dist(name):
+        dy = float((outs[name] - outs["fp64"]).abs().max() / outs["fp64"].abs().max())
+        num = sum(float(((grads[name][k] - grads["fp64"][k]) ** 2).sum()) for k in grads["fp64"])
+        den = sum(float((grads["fp64"][k] ** 2).sum()) for k in grads["fp64"])
+        return dy, (num / den) ** 0.5
+    hy, hg = dist("hip")
+    ry, rg = dist("rocm")
+    report("monodepth2_network", case=tag, hip_y=f"{hy:.2e}", hip_grad=f"{hg:.2e}", rocm_y=f"{ry:.2e}", rocm_grad=f"{rg:.2e}")
+    assert hy <= max(4 * ry, 1e-5) and hg <= max(4 * rg, 1e-4), (hy, ry, hg, rg)
+
+
+def test_network_matches_fp64_twin_small_feed():
+    import torch
+    from consistent_depth_amd.monodepth.monodepth2_net import Monodepth2Net
+    torch.manual_seed(0)
+    net = Monodepth2Net((64, 192))
+    net = net.cuda().train()
+    images = torch.rand(4, 3, 48, 160, dtype=torch.float64, generator=torch.Generator().manual_seed(1)).float()
+    _compare_with_twin(net, net, images, (64, 192), "feed 64x192, 4 x 48x160")
+
+
+def test_adapter_matches_fp64_twin_at_the_real_feed():
+    import torch
+    from consistent_depth_amd.monodepth.depth_model_registry import get_depth_model
+    model = get_depth_model("monodepth2")(seed=0)
+    assert (model.feed_height, model.feed_width) == (320, 1024) and not model.pretrained
+    model.train()
+    images = torch.rand(1, 2, 3, 224, 384, generator=torch.Generator().manual_seed(2))
+
+    def run(x):
+        out = model.estimate_raw(x.reshape(1, 2, 3, 224, 384))
+        assert out.shape == (1, 2, 224, 384)
+        return out.reshape(2, 1, 224, 384)
+    _compare_with_twin(model.model, run, images.reshape(2, 3, 224, 384), (320, 1024), "feed 320x1024, 2 x 224x384")
+
+
+# ------------------------------------------------------------------------------------------------------------------ the step
+def _batch(B, H, W, seed):
+    import torch
+    from consistent_depth_amd import synthetic
+    b = synthetic.make_scene_batch(B, H, W, seed=seed)
+    t = lambda a: torch.tensor(a, device="cuda")  # noqa: E731
+    meta = {"intrinsics": t(b["intrinsics"]), "extrinsics": t(b["extrinsics"]),
+            "geometry_consistency": {"flows": [t(f) for f in b["flows"]], "masks": [t(m) for m in b["masks"]]}}
+    images = torch.rand(B, 2, 3, H, W, generator=torch.Generator().manual_seed(seed)).cuda()
+    return images, meta
+
+
+def _params(lr):
+    import argparse
+    return argparse.Namespace(lambda_reprojection=1.0, lambda_view_baseline=1.0, lambda_parameter=0, learning_rate=lr, optimizer="Adam")
+
+
+_FROZEN = ("encoder.encoder.fc.", "depth_decoder.decoder.11.", "depth_decoder.decoder.12.", "depth_decoder.decoder.13.")
+
+
+def test_one_finetune_step_and_loss_goes_down():
+    import torch
+    from consistent_depth_amd.engine import FineTuneStep
+    from consistent_depth_amd.monodepth.depth_model_registry import get_depth_model
+    cls = get_depth_model("monodepth2")
+    assert (cls.align, cls.learning_rate, cls.lambda_view_baseline) == (1, 0.00004, 1)
+    model = cls(seed=0, feed=(64, 192))
+    model.train()
+    step = FineTuneStep(model, _params(cls.learning_rate), world=1)
+    images, meta = _batch(2, 48, 64, seed=1)
+    before = {k: p.detach().clone() for k, p in model.model.named_parameters()}
+    loss, parts = step(images, meta)
+    assert torch.isfinite(loss).all() and set(parts) == {"reprojection", "disparity"}
+    moved = [k for k, p in model.model.named_parameters() if not torch.equal(p, before[k])]
+    frozen = [k for k in before if k.startswith(_FROZEN)]
+    assert len(frozen) == 8 and not set(frozen) & set(moved)        # zero gradients leave them bit-for-bit unchanged
+    assert set(moved) == set(before) - set(frozen)
+    with torch.no_grad():
+        depth = model.forward(images)
+    assert depth.shape == (2, 2, 48, 64) and torch.isfinite(depth).all() and (depth > 0).all()
+    # ten steps on one fixed batch at lr 1e-4 lower its loss
+    model2 = cls(seed=0, feed=(64, 192))
+    model2.train()
+    step2 = FineTuneStep(model2, _params(1e-4), world=1)
+    losses = [float(step2(images, meta)[0]) for _ in range(11)]
+    report("monodepth2_ten_steps", first=f"{losses[0]:.5f}", last=f"{losses[-1]:.5f}")
+    assert np.isfinite(losses).all() and losses[-1] < losses[0], losses
+
+
+def test_graphed_step_matches_eager():
+    import torch
+    from consistent_depth_amd.engine import FineTuneStep, GraphedFineTuneStep
+    from consistent_depth_amd.monodepth.depth_model_registry import get_depth_model
+    images, meta = _batch(2, 48, 64, seed=4)
+    flats = {}
+    for mode in ("eager", "graphed"):
+        model = get_depth_model("monodepth2")(seed=3, feed=(64, 192))
+        model.train()
+        step = FineTuneStep(model, _params(4e-5), world=1)
+        run = GraphedFineTuneStep(step) if mode == "graphed" else step
+        for _ in range(4):
+            run(images, meta)
+        torch.cuda.synchronize()
+        if mode == "graphed":
+            assert run.graphed is True, run.capture_error
+        flats[mode] = step.opt.flat_param.detach().clone()
+    a, b = flats["graphed"], flats["eager"]
+    rel = float((a - b).norm() / b.norm())
+    report("monodepth2_graphed_vs_eager", rel=f"{rel:.2e}", bitwise=bool(torch.equal(a, b)))
+    assert rel <= 1e-6, rel
+
+
+def test_upstream_format_weights_load(tmp_path, monkeypatch):
+    import torch
+    from consistent_depth_amd.monodepth.monodepth2_model import Monodepth2Model
+    src = Monodepth2Model(seed=5, feed=(64, 128))
+    enc = dict(src.model.encoder.state_dict())
+    enc.update(height=64, width=128, use_stereo=True)
+    torch.save(enc, str(tmp_path / "encoder.pth"))
+    torch.save(src.model.depth_decoder.state_dict(), str(tmp_path / "depth.pth"))
+    monkeypatch.setenv("CD_AMD_MONODEPTH2_WEIGHTS", str(tmp_path))
+    dst = Monodepth2Model()            # seed 0, default feed: everything comes from the files
+    assert dst.pretrained and (dst.feed_height, dst.feed_width) == (64, 128)
+    for k, v in src.model.state_dict().items():
+        assert torch.equal(v, dst.model.state_dict()[k]), k
+    images = torch.rand(1, 2, 3, 40, 72, device="cuda")
+    src.eval()
+    dst.eval()
+    with torch.no_grad():
+        a, b = src.estimate_raw(images), dst.estimate_raw(images)
+    assert a.shape == (1, 2, 40, 72) and torch.equal(a, b)
+    monkeypatch.setenv("CD_AMD_MONODEPTH2_WEIGHTS", str(tmp_path / "missing"))
+    with pytest.raises(FileNotFoundError):
+        Monodepth2Model()
+
+
+def test_step_runs_no_framework_layer_kernels():
+    import re
+    import torch
+    from consistent_depth_amd.engine import FineTuneStep
+    from consistent_depth_amd.monodepth.depth_model_registry import get_depth_model
+    model = get_depth_model("monodepth2")(seed=0, feed=(64, 192))
+    model.train()
+    step = FineTuneStep(model, _params(4e-5), world=1)
+    images, meta = _batch(2, 48, 64, seed=2)
+    for _ in range(2):
+        step(images, meta)
+    torch.cuda.synchronize()
+    from torch.profiler import ProfilerActivity, profile
+    try:
+        with profile(activities=[ProfilerActivity.CUDA, ProfilerActivity.CPU]) as prof:
+            step(images, meta)
+            torch.cuda.synchronize()
+        events = list(prof.events())
+    except Exception as e:   # noqa: BLE001 -- the tracer, not the step
+        pytest.skip(f"torch.profiler is not usable on this stack: {type(e).__name__}: {e}")
+    kernels = [e.name for e in events if str(getattr(e, "device_type", "")).endswith("CUDA") and e.name
+               and not getattr(e, "is_user_annotation", False) and "#" not in e.name]
+    if not any("cd::" in k for k in kernels):
+        pytest.skip(f"torch.profiler reports no device kernels of this package on this stack ({len(kernels)} device events)")
+    foreign = sorted({k for k in kernels if "cd::" not in k and "rocclr" not in k.lower() and not k.lower().startswith(("memcpy", "memset"))})
+    report("monodepth2_foreign_kernels", n=len(foreign), names="; ".join(f[:80] for f in foreign))
+    layer = re.compile(r"conv|batch_?norm|bn_|miopen|gemm|upsample|interp|bicubic|nearest|elu|sigmoid|reflect|cat|pad", re.I)
+    bad = [k for k in foreign if layer.search(k)]
+    assert not bad, bad
+
+
+def test_cli_kitti_configure_finetunes_end_to_end(tmp_path):
+    sys.path.insert(0, os.path.join(REPO, "tools"))
+    import make_synthetic_dataset as msd
+    from consistent_depth_amd.depth_fine_tuning import make_tag
+    from consistent_depth_amd.params import Video3dParamsParser
+    from consistent_depth_amd.process import DatasetProcessor
+    from consistent_depth_amd.utils import image_io
+
+    path = str(tmp_path / "clip")
+    range_dir, pairs = msd.write_dataset(path, n_frames=6, H=64, W=48, seed=3, model_type="monodepth2")
+    params = Video3dParamsParser().parse(["--path", path, "--configure", "kitti", "--num_epochs", "2", "--batch_size", "4"])
+    assert params.model_type == "monodepth2" and params.learning_rate == 0.00004 and params.lambda_view_baseline == 1
+    _, out_dir, frames = DatasetProcessor().process(params)
+    assert out_dir == os.path.join(range_dir, make_tag(params)) and frames == list(range(6))
+    n = len(pairs)
+    for epoch, it in ((0, 0), (1, n), (2, 2 * n)):
+        with open(os.path.join(out_dir, "eval", f"loss_e{epoch:04d}_iter{it:06d}.json")) as f:
+            d = json.load(f)
+        assert set(d["reprojection"]) == set(d["disparity"]) == {str([i, j]) for i, j in pairs}
+        for fr in range(6):
+            inv = image_io.load_raw_float32_image(os.path.join(out_dir, "eval", f"depth_{fr:06d}_e{epoch:04d}_iter{it:06d}.raw"))
+            assert inv.shape == (64, 48) and np.isfinite(inv).all() and (inv > 0).all()
+    for fr in range(6):
+        inv = image_io.load_raw_float32_image(os.path.join(out_dir, "depth", f"frame_{fr:06d}.raw"))
+        assert inv.shape == (64, 48) and np.isfinite(inv).all() and (inv > 0).all()
+    assert not [f for f in os.listdir(os.path.join(out_dir, "checkpoints")) if f.endswith(".pth")]     # save() is a no-op
