@@ -4,7 +4,8 @@
 // these: its BatchNorm statistics come out of the convolution epilogues and are applied on load (layers.hip).
 //
 // All HBM-bound, one pass each:
-//   forward   stats   : per-channel (sum, sum of squares)  -- fp32 per block, fp64 across blocks (CD_BN_STAT_SLOTS partial copies)
+//   forward   stats   : per-channel (sum, sum of squares)  -- fp32 per block of (x - the channel's first element), shifted back and summed
+//                       across blocks in fp64 (CD_BN_STAT_SLOTS partial copies)
 //             finalize: cd_bn_finalize (layers.hip): mean, invstd, scale = gamma invstd, shift = beta - gamma mean invstd, running statistics
 //             apply   : y = act(fma(x, scale, shift) [+ res])
 //   backward  reduce  : dv = relu ? (y > 0 ? dy : 0) : dy;  T1 = sum dv, T2 = sum dv * xhat;  [dres = dv]
@@ -26,23 +27,33 @@ __global__ __launch_bounds__(kBlock) void bnb_stats_kernel(const float* __restri
     __shared__ float lds[kBlock / kWave];
     const int c = blockIdx.y, n = blockIdx.z;
     const float* p = x + ((size_t)n * C + c) * HW;
+    // Shifted sums: the fp32 partials are of x - pivot (the channel's first element), shifted back in fp64 below.  Partials of x and x^2
+    // lose the variance to cancellation when |mean| >> std (E[x^2] - mean^2 at 655 360 samples: 6e-5 of the output at |mean| = 100 std);
+    // in fp64 the same cancellation costs nothing.
+    const float piv = x[(size_t)c * HW];
+    const bool vec = (HW & 3) == 0;
     float s = 0.f, q = 0.f;
-    if ((HW & 3) == 0) {
+    if (vec) {
         const float4* p4 = reinterpret_cast<const float4*>(p);
         for (int i = blockIdx.x * kBlock + threadIdx.x; i < HW / 4; i += gridDim.x * kBlock) {
             const float4 v = p4[i];
-            s += (v.x + v.y) + (v.z + v.w);
-            q += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+            const float a = v.x - piv, b = v.y - piv, e = v.z - piv, f = v.w - piv;
+            s += (a + b) + (e + f);
+            q += (a * a + b * b) + (e * e + f * f);
         }
     } else {
-        for (int i = blockIdx.x * kBlock + threadIdx.x; i < HW; i += gridDim.x * kBlock) { const float v = p[i]; s += v; q += v * v; }
+        for (int i = blockIdx.x * kBlock + threadIdx.x; i < HW; i += gridDim.x * kBlock) { const float v = p[i] - piv; s += v; q += v * v; }
     }
     s = block_sum(s, lds);
     q = block_sum(q, lds);
     if (threadIdx.x == 0) {
+        // samples this block summed: indices blockIdx.x * kBlock + t + k * stride (t < kBlock) below `units`
+        const int units = vec ? HW / 4 : HW, stride = gridDim.x * kBlock, rem = units % stride;
+        const int mine = (units / stride) * kBlock + min(max(rem - (int)blockIdx.x * kBlock, 0), kBlock);
+        const double cnt = (double)mine * (vec ? 4 : 1), pd = (double)piv, sd = (double)s;
         const int slot = (blockIdx.x + n) % CD_BN_STAT_SLOTS;
-        atomicAdd(&stats[((size_t)slot * C + c) * 2], (double)s);
-        atomicAdd(&stats[((size_t)slot * C + c) * 2 + 1], (double)q);
+        atomicAdd(&stats[((size_t)slot * C + c) * 2], sd + cnt * pd);                              // sum x   = sum (x - p) + cnt p
+        atomicAdd(&stats[((size_t)slot * C + c) * 2 + 1], (double)q + pd * (2.0 * sd + cnt * pd));  // sum x^2 = sum (x - p)^2 + 2 p sum (x - p) + cnt p^2
     }
 }
 

@@ -10,6 +10,7 @@ import pytest
 
 from conftest import REPO
 from tests.gpu_util import report
+from tests.monodepth2_twin import twin as _twin
 
 pytestmark = [pytest.mark.gpu]
 
@@ -148,97 +149,7 @@ def test_crop_act_matches_aten(shape, act):
 
 
 # ------------------------------------------------------------------------------------------------------------------ fp64 twin
-def _twin(feed):
-    """Upstream's ResnetEncoder(18) + DepthDecoder from the ATen modules (nn.Conv2d, BatchNorm2d, ReflectionPad2d, ELU, F.interpolate) and
-    monodepth2_model.estimate_depth's steps up to the disparity at frame size."""
-    import torch
-    import torch.nn as nn
-    import torch.nn.functional as F
-
-    class Block(nn.Module):
-        def __init__(self, cin, p, s):
-            super().__init__()
-            self.conv1, self.bn1 = nn.Conv2d(cin, p, 3, s, 1, bias=False), nn.BatchNorm2d(p)
-            self.conv2, self.bn2 = nn.Conv2d(p, p, 3, 1, 1, bias=False), nn.BatchNorm2d(p)
-            self.downsample = nn.Sequential(nn.Conv2d(cin, p, 1, s, bias=False), nn.BatchNorm2d(p)) if (s != 1 or cin != p) else None
-
-        def forward(self, x):
-            idt = x if self.downsample is None else self.downsample(x)
-            return F.relu(self.bn2(self.conv2(F.relu(self.bn1(self.conv1(x))))) + idt)
-
-    class ResNet(nn.Module):
-        def __init__(self):
-            super().__init__()
-            self.conv1, self.bn1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False), nn.BatchNorm2d(64)
-            cin = 64
-            for i, (p, s) in enumerate(((64, 1), (128, 2), (256, 2), (512, 2)), start=1):
-                setattr(self, f"layer{i}", nn.Sequential(Block(cin, p, s), Block(p, p, 1)))
-                cin = p
-            self.fc = nn.Linear(512, 1000)
-
-    class Encoder(nn.Module):
-        def __init__(self):
-            super().__init__()
-            self.encoder = ResNet()
-
-        def forward(self, x):
-            e = self.encoder
-            f = [F.relu(e.bn1(e.conv1((x - 0.45) / 0.225)))]
-            f.append(e.layer1(F.max_pool2d(f[-1], 3, 2, 1)))
-            for layer in (e.layer2, e.layer3, e.layer4):
-                f.append(layer(f[-1]))
-            return f
-
-    class Conv3x3(nn.Module):
-        def __init__(self, cin, cout):
-            super().__init__()
-            self.pad, self.conv = nn.ReflectionPad2d(1), nn.Conv2d(cin, cout, 3)
-
-        def forward(self, x):
-            return self.conv(self.pad(x))
-
-    class ConvBlock(nn.Module):
-        def __init__(self, cin, cout):
-            super().__init__()
-            self.conv, self.nonlin = Conv3x3(cin, cout), nn.ELU(inplace=True)
-
-        def forward(self, x):
-            return self.nonlin(self.conv(x))
-
-    class Decoder(nn.Module):
-        def __init__(self):
-            super().__init__()
-            enc, dec = (64, 64, 128, 256, 512), (16, 32, 64, 128, 256)
-            convs = []
-            for i in range(4, -1, -1):
-                convs += [ConvBlock(enc[-1] if i == 4 else dec[i + 1], dec[i]), ConvBlock(dec[i] + (enc[i - 1] if i > 0 else 0), dec[i])]
-            convs += [Conv3x3(dec[s], 1) for s in range(4)]
-            self.decoder = nn.ModuleList(convs)
-
-        def forward(self, f):
-            x = f[-1]
-            for j, i in enumerate(range(4, -1, -1)):
-                x = [F.interpolate(self.decoder[2 * j](x), scale_factor=2, mode="nearest")]
-                if i > 0:
-                    x.append(f[i - 1])
-                x = self.decoder[2 * j + 1](torch.cat(x, 1))
-            return torch.sigmoid(self.decoder[10](x))
-
-    class Twin(nn.Module):
-        def __init__(self):
-            super().__init__()
-            self.encoder, self.depth_decoder = Encoder(), Decoder()
-
-        def forward(self, images):
-            H, W = images.shape[-2:]
-            x = F.interpolate(images, size=feed, mode="bicubic", align_corners=False)
-            disp = self.depth_decoder(self.encoder(x))
-            return F.interpolate(disp, size=(H, W), mode="bicubic", align_corners=False)
-
-    return Twin()
-
-
-def _compare_with_twin(hip_net, run_hip, images, feed, tag):
+def _compare_with_twin(hip_net, run_hip, images, feed, tag, per_tensor_floor=None):
     import torch
     twins = {}
     for name in ("rocm", "fp64"):
@@ -269,6 +180,23 @@ def _compare_with_twin(hip_net, run_hip, images, feed, tag):
     ry, rg = dist("rocm")
     report("monodepth2_network", case=tag, hip_y=f"{hy:.2e}", hip_grad=f"{hg:.2e}", rocm_y=f"{ry:.2e}", rocm_grad=f"{rg:.2e}")
     assert hy <= max(4 * ry, 1e-5) and hg <= max(4 * rg, 1e-4), (hy, ry, hg, rg)
+    if per_tensor_floor is None:
+        return
+    # the global norm above cannot see a local error (one bias gradient, one BatchNorm's d gamma, a shortcut of layer4): every parameter
+    # tensor on its own, against the ATen fp32 twin's distance for that tensor
+    per = {}
+    for k, ref in grads["fp64"].items():
+        den = max(float(ref.norm()), 1e-300)
+        per[k] = (float((grads["hip"][k] - ref).norm()) / den, float((grads["rocm"][k] - ref).norm()) / den)
+    ratio = sorted(per, key=lambda k: per[k][0] / max(4 * per[k][1], per_tensor_floor), reverse=True)
+    hs = np.array([v[0] for v in per.values()])
+    rs = np.array([v[1] for v in per.values()])
+    report("monodepth2_network_per_tensor", case=tag, n=len(per), floor=per_tensor_floor,
+           hip_quantiles="/".join(f"{q:.1e}" for q in np.quantile(hs, [0.1, 0.5, 0.9, 1.0])),
+           rocm_quantiles="/".join(f"{q:.1e}" for q in np.quantile(rs, [0.1, 0.5, 0.9, 1.0])),
+           tightest="; ".join(f"{k} {per[k][0]:.1e}/{per[k][1]:.1e}" for k in ratio[:6]))
+    bad = {k: per[k] for k in ratio if per[k][0] > max(4 * per[k][1], per_tensor_floor)}
+    assert not bad, bad
 
 
 def test_network_matches_fp64_twin_small_feed():
@@ -279,6 +207,14 @@ def test_network_matches_fp64_twin_small_feed():
     net = net.cuda().train()
     images = torch.rand(4, 3, 48, 160, dtype=torch.float64, generator=torch.Generator().manual_seed(1)).float()
     _compare_with_twin(net, net, images, (64, 192), "feed 64x192, 4 x 48x160")
+
+
+# Per-tensor floor, from the distribution of the 82 tensors' distances (relative L2, 2 images at the feed): HIP 2.9e-5 / 3.6e-3 / 9.3e-3 /
+# 1.1e-2 at the 10 / 50 / 90 / 100 % quantiles, the ATen fp32 twin 1.7e-5 / 3.3e-3 / 1.1e-2 / 1.4e-2 (ReLU-mask flips make most tensors
+# noisy in both).  The tensors below 4x the twin are the decoder's bias gradients, the tightest upconv(0,0)'s: 9.0e-5 against the twin's
+# 1.1e-5 -- the split-bf16 arithmetic's systematic error seen through a sum that cancels (tests/test_monodepth2_layers_gpu.py::_BLOCK_BOUND).
+# 2e-4 keeps 2x margin over it and stays 5x below a 1e-3 error in one tensor.
+_PER_TENSOR_FLOOR = 2e-4
 
 
 def test_adapter_matches_fp64_twin_at_the_real_feed():
@@ -293,7 +229,8 @@ def test_adapter_matches_fp64_twin_at_the_real_feed():
         out = model.estimate_raw(x.reshape(1, 2, 3, 224, 384))
         assert out.shape == (1, 2, 224, 384)
         return out.reshape(2, 1, 224, 384)
-    _compare_with_twin(model.model, run, images.reshape(2, 3, 224, 384), (320, 1024), "feed 320x1024, 2 x 224x384")
+    _compare_with_twin(model.model, run, images.reshape(2, 3, 224, 384), (320, 1024), "feed 320x1024, 2 x 224x384",
+                       per_tensor_floor=_PER_TENSOR_FLOOR)
 
 
 # ------------------------------------------------------------------------------------------------------------------ the step
