@@ -13,7 +13,7 @@ import torch  # imported first on purpose: libcd_amd.so then binds to torch's li
 _PKG = os.path.dirname(os.path.abspath(__file__))
 # CD_AMD_LIB: load another build of the SAME library (A/B measurements of kernel variants, tools/exp/build_variants.sh); not a fallback
 SO_PATH = os.environ.get("CD_AMD_LIB") or os.path.join(_PKG, "libcd_amd.so")
-ABI_VERSION = 10
+ABI_VERSION = 11
 BN_STAT_SLOTS = 16   # CD_BN_STAT_SLOTS of include/consistent_depth_amd.h (checked by tests/test_abi.py)
 
 _lib = None
@@ -52,6 +52,12 @@ SIGNATURES = {
     "cd_conv2d_fwd_grouped": (c_i, [c_p, c_i, c_i, c_i, c_p, c_sz, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
     "cd_conv2d_fwd_multi": (c_i, [c_p, c_i, c_i, c_i, c_p]),
     "cd_conv2d_wgrad_grouped": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_sz, c_i, c_i, c_i, c_i, c_p]),
+    "cd_conv2d_strided_supported": (c_i, [c_i, c_i, c_i, c_i, c_i]),
+    "cd_conv2d_fwd_strided": (c_i, [c_p, c_i, c_i, c_i, c_p, c_sz, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "cd_conv2d_dgrad_strided": (c_i, [c_p, c_i, c_i, c_i, c_p, c_sz, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "cd_conv2d_wgrad_strided": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_sz, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "cd_subsample2_fwd": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_p]),
+    "cd_subsample2_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
     "cd_set_conv_arith": (c_i, [c_i]),
     "cd_get_conv_arith": (c_i, []),
     "cd_debug_force_conv_tile_rows": (c_i, [c_i]),

@@ -20,6 +20,7 @@
 #include "cd_common.h"
 #include "conv_split.h"
 #include "wgrad_split.h"
+#include "conv_strided.h"
 
 namespace cd {
 
@@ -605,6 +606,21 @@ static WgLayout wgrad_layout(int Cout, int Cin, int ks, int N, int H, int W, int
     L.max_splits = wgrad_splits(L.cogs * L.cigs, per_cu, 1 << 30);
     L.splits = N > 0 ? wgrad_splits(L.cogs * L.cigs, per_cu, wgrad_items(N, H, W, ty)) : L.max_splits;
     return L;
+}
+
+// ---- for conv_strided.hip: the split layout's geometry and its unpack (the stride-2 weight gradient writes the same packed slices)
+void wgrad_split_layout_info(int Cout, int Cin, int ks, int* cogs, int* cigs, int* max_splits, size_t* slice) {
+    const WgLayout L = wgrad_layout_split(Cout, Cin, ks, 0, 0, 0);
+    *cogs = L.cogs; *cigs = L.cigs; *max_splits = L.max_splits; *slice = L.slice;
+}
+
+int launch_unpack_wgrad_split(const float* workspace, int Cout, int Cin, int ks, int cigs, int splits, size_t slice, float* dw, int accumulate,
+                              int groups, size_t ws_group_stride, hipStream_t s) {
+    const int total = Cout * Cin * ks * ks;
+    const int bx = (total + 255) / 256 > 64 ? 64 : (total + 255) / 256;
+    hipLaunchKernelGGL(unpack_wgrad_kernel, dim3(bx, groups), dim3(256), 0, s, workspace, Cout, Cin, ks, 16, 16, cigs, splits, slice, dw, accumulate,
+                       ws_group_stride);
+    return hipGetLastError() == hipSuccess ? CD_OK : CD_ERR_LAUNCH;
 }
 
 }  // namespace cd

@@ -445,3 +445,80 @@ class PackTable:
         rc = _native.lib().cd_conv2d_pack_weights_table(self._table.data_ptr(), len(self._sources),
                                                         _native.stream_ptr(self.device))
         _native.check(rc, "cd_conv2d_pack_weights_table")
+
+
+# ---------------------------------------------------------------- stride 2 (cd_conv2d_*_strided, cd_subsample2_*)
+def strided_enabled() -> bool:
+    """CD_AMD_CONV_STRIDED=0: HipConv2d keeps the stride-1-plus-sub-sampling path everywhere (A/B on one box)."""
+    return os.environ.get("CD_AMD_CONV_STRIDED", "1") != "0"
+
+
+def strided_supported(pass_, ks, stride, cin_g, cout_g) -> bool:
+    """cd_conv2d_strided_supported under the current arithmetic mode (mode 0 has no strided kernels).
+    pass_: 0 forward, 1 input gradient, 2 weight gradient."""
+    lib = _native.lib()
+    return bool(lib.cd_conv2d_strided_supported(pass_, ks, stride, cin_g, cout_g)) and lib.cd_get_conv_arith() >= 1
+
+
+def _group_stride(packed_w, groups):
+    if groups == 1:
+        return 0
+    assert packed_w.numel() % groups == 0, "packed_w: `groups` equally sized packed filters side by side"
+    return packed_w.numel() // groups
+
+
+def conv2d_strided(x, packed_w, cin_g, cout_g, ks, groups=1, bias=None, x_coff=0, out=None, y_coff=0, accumulate=False, stride=2):
+    """out[:, y_coff : y_coff + groups*cout_g] (+)= conv(x[:, x_coff : x_coff + groups*cin_g], stride 2, padding (ks-1)/2) + bias.
+    packed_w: the forward packs (pack_weights of (cout_g, cin_g, ks)) of all groups side by side.  x is (N, *, H, W), out
+    (N, *, ceil(H/2), ceil(W/2))."""
+    N, x_ctot, H, W = x.shape
+    if out is None:
+        out = torch.empty(N, groups * cout_g, (H + 1) // 2, (W + 1) // 2, dtype=torch.float32, device=x.device)
+    rc = _native.lib().cd_conv2d_fwd_strided(
+        _native.dev_ptr(x, "x"), x_ctot, x_coff, cin_g, _native.dev_ptr(packed_w, "packed_w"), _group_stride(packed_w, groups),
+        _native.dev_ptr(bias, "bias") if bias is not None else None, _native.dev_ptr(out, "out"), out.shape[1], y_coff, cout_g, groups,
+        int(accumulate), N, H, W, ks, stride, _native.stream_ptr(x.device))
+    _native.check(rc, "cd_conv2d_fwd_strided")
+    return out
+
+
+def conv2d_dgrad_strided(dy, packed_wT, cin_g, cout_g, ks, dx, groups=1, dy_coff=0, dx_coff=0, accumulate=False, stride=2):
+    """dx[:, dx_coff : dx_coff + groups*cin_g] (+)= the input gradient of conv2d_strided; dx (N, *, H, W) fixes the un-strided
+    extents, dy is (N, *, ceil(H/2), ceil(W/2)).  packed_wT: the transposed packs of all groups.  Every element is written."""
+    N, dx_ctot, H, W = dx.shape
+    rc = _native.lib().cd_conv2d_dgrad_strided(
+        _native.dev_ptr(dy, "dy"), dy.shape[1], dy_coff, cout_g, _native.dev_ptr(packed_wT, "packed_wT"), _group_stride(packed_wT, groups),
+        _native.dev_ptr(dx, "dx"), dx_ctot, dx_coff, cin_g, groups, int(accumulate), N, H, W, ks, stride, _native.stream_ptr(dx.device))
+    _native.check(rc, "cd_conv2d_dgrad_strided")
+    return dx
+
+
+def conv2d_wgrad_strided(x, dy, cin_g, cout_g, ks, dw, workspace, groups=1, x_coff=0, dy_coff=0, accumulate=False, stride=2):
+    """dw (groups*cout_g, cin_g, ks, ks) (+)= the weight gradient of conv2d_strided.  workspace: `groups` equal parts of at
+    least wgrad_workspace_floats(cout_g, cin_g, ks) floats."""
+    N, x_ctot, H, W = x.shape
+    rc = _native.lib().cd_conv2d_wgrad_strided(
+        _native.dev_ptr(x, "x"), x_ctot, x_coff, cin_g, _native.dev_ptr(dy, "dy"), dy.shape[1], dy_coff, cout_g, groups,
+        _native.dev_ptr(dw, "dw"), int(accumulate), _native.dev_ptr(workspace, "workspace"), workspace.numel() // groups, N, H, W, ks, stride,
+        _native.stream_ptr(x.device))
+    _native.check(rc, "cd_conv2d_wgrad_strided")
+    return dw
+
+
+def subsample2(x, C=None, coff=0, out=None):
+    """out (N, C, ceil(H/2), ceil(W/2)) = x[:, coff : coff + C, ::2, ::2]."""
+    N, ctot, H, W = x.shape
+    C = ctot - coff if C is None else C
+    if out is None:
+        out = torch.empty(N, C, (H + 1) // 2, (W + 1) // 2, dtype=torch.float32, device=x.device)
+    _native.check(_native.lib().cd_subsample2_fwd(_native.dev_ptr(x, "x"), ctot, coff, C, _native.dev_ptr(out, "out"), N, H, W,
+                                                  _native.stream_ptr(x.device)), "cd_subsample2_fwd")
+    return out
+
+
+def subsample2_bwd(dy, dx, coff=0):
+    """dx[:, coff : coff + C] = dy (N, C, ceil(H/2), ceil(W/2)) at even rows / columns, 0 elsewhere (the whole plane is written)."""
+    N, ctot, H, W = dx.shape
+    _native.check(_native.lib().cd_subsample2_bwd(_native.dev_ptr(dy, "dy"), _native.dev_ptr(dx, "dx"), ctot, coff, dy.shape[1], N, H, W,
+                                                  _native.stream_ptr(dx.device)), "cd_subsample2_bwd")
+    return dx

@@ -9,8 +9,11 @@ Same parameters and state_dict keys as nn.Conv2d (a checkpoint loads unchanged).
     issued one launch per group (32 x 33 bottlenecks x {forward, input gradient, weight gradient + unpack} = 4224 launches
     per step, which made the MiDaS step host-bound: 222 ms of enqueue for a 243 ms step).  At 8 channels per group a
     16-wide MFMA column tile is half empty;
-  * stride 2: the stride-1 "same" output sampled at even positions (identical values; 4x the MACs of a strided kernel --
-    only the stem, 3 bottlenecks and 3 down-sample 1x1 of ResNeXt-101 are strided).
+  * stride 2: native kernels (csrc/conv_strided.hip) wherever cd_conv2d_strided_supported says yes -- 3x3 with >= 8 input channels per
+    group, dense and grouped, on cd_conv2d_fwd_strided / _dgrad_strided / _wgrad_strided (no full-resolution output, no zero-stuffed
+    gradient); 1x1 on cd_subsample2_fwd / _bwd around the stride-1 1x1 kernels.  Elsewhere (the RGB stems, arithmetic mode 0, or
+    CD_AMD_CONV_STRIDED=0 for A/B runs) the stride-1 "same" output sampled at even positions: identical values, 4x the MACs of a
+    strided kernel and framework copy / fill kernels around it.
   * 1x1, dense (the bottleneck entry / exit convolutions: 2/3 of ResNeXt-101's multiply-adds, at 12x12 .. 96x96 images with
     256 .. 2048 channels): a plain GEMM  Y[n] = W [Cout x Cin] . X[n] [Cin x HW]  -- not a stencil.  On the hand-written kernels like
     everything else (no library GEMM on the path; rounds 3-5 carried a torch.matmul / bmm route behind CD_AMD_MIDAS_1X1=gemm, removed in
@@ -99,13 +102,24 @@ class _HipConvFn(torch.autograd.Function):
     def forward(ctx, x, weight, bias, layer):
         Cout, cin_g, ks, _ = weight.shape
         G, s = layer.groups, layer.stride[0]
+        cout_g = Cout // G
         ctx.full_hw = None
+        # stride 2 on the native kernels wherever the library has them (CD_AMD_CONV_STRIDED=0, arithmetic mode 0, the RGB stems: the
+        # stride-1-plus-sub-sampling path below)
+        ctx.native_s2 = s == 2 and C.strided_enabled() and all(C.strided_supported(p, ks, 2, cin_g, cout_g) for p in (0, 1, 2))
+        if ctx.native_s2 and ks == 3:
+            x = x.contiguous()
+            layer._packed(weight)
+            y = C.conv2d_strided(x, layer._arena, cin_g, cout_g, ks, groups=G, bias=bias)
+            ctx.layer, ctx.hw, ctx.s = layer, tuple(x.shape[2:]), s
+            ctx.save_for_backward(x, weight)
+            ctx.has_bias = bias is not None
+            return y
         if ks == 1 and s > 1:      # a strided 1x1 reads only the sampled pixels: sub-sample FIRST (exact, s^2 fewer multiply-adds)
             ctx.full_hw = tuple(x.shape[2:])
-            x, s = x[:, :, ::s, ::s], 1
+            x, s = (C.subsample2(x.contiguous()) if ctx.native_s2 else x[:, :, ::s, ::s]), 1
         x = x.contiguous()
         N, Cin, H, W = x.shape
-        cout_g = Cout // G
         lib, stream = _native.lib(), _native.stream_ptr(x.device)
         pk, _ = layer._packed(weight)
         y = torch.empty(N, Cout, H, W, dtype=torch.float32, device=x.device)
@@ -131,6 +145,8 @@ class _HipConvFn(torch.autograd.Function):
         G, s = layer.groups, ctx.s
         cout_g = Cout // G
         lib, stream = _native.lib(), _native.stream_ptr(x.device)
+        if ctx.native_s2 and ks == 3:
+            return _HipConvFn._backward_strided(ctx, dy)
         if s > 1:   # adjoint of the sub-sampling: zeros between the samples
             dyf = torch.zeros(N, Cout, H, W, dtype=torch.float32, device=dy.device)
             dyf[:, :, ::s, ::s] = dy
@@ -165,9 +181,12 @@ class _HipConvFn(torch.autograd.Function):
                 _native.check(rc, "cd_conv2d_fwd_grouped (dgrad)")
             if ctx.full_hw is not None:      # (strided 1x1: the input was sub-sampled first)
                 st = layer.stride[0]
-                full = torch.zeros((N, Cin) + ctx.full_hw, dtype=dx.dtype, device=dx.device)
-                full[:, :, ::st, ::st] = dx
-                dx = full
+                if ctx.native_s2:      # the whole plane in one pass: values at even positions, zeros elsewhere
+                    dx = C.subsample2_bwd(dx, torch.empty((N, Cin) + ctx.full_hw, dtype=dx.dtype, device=dx.device))
+                else:
+                    full = torch.zeros((N, Cin) + ctx.full_hw, dtype=dx.dtype, device=dx.device)
+                    full[:, :, ::st, ::st] = dx
+                    dx = full
         if side is not None:
             done = torch.cuda.Event()
             done.record(side)
@@ -181,6 +200,45 @@ class _HipConvFn(torch.autograd.Function):
         if ctx.has_bias and ctx.needs_input_grad[2]:
             from .layers import channel_sum      # (hand-written reduction: cd_channel_sum)
             dyc = dy.contiguous()
+            db = torch.empty(Cout, dtype=torch.float32, device=dy.device)
+            channel_sum(dyc, 0, Cout, db)
+        return dx, dw, db, None
+
+    @staticmethod
+    def _backward_strided(ctx, dy):
+        """3x3 / 2 on cd_conv2d_dgrad_strided / cd_conv2d_wgrad_strided: no zero-stuffed dy, the weight gradient on the side stream
+        as in the stride-1 backward."""
+        x, weight = ctx.saved_tensors
+        layer = ctx.layer
+        Cout, cin_g, ks, _ = weight.shape
+        G = layer.groups
+        cout_g = Cout // G
+        dyc = dy.contiguous()
+        dx = dw = db = None
+
+        def wgrad():
+            out = torch.empty_like(weight)
+            ws, _ = layer._wgrad_workspace(cout_g, cin_g, ks, x.device)
+            return C.conv2d_wgrad_strided(x, dyc, cin_g, cout_g, ks, out, ws, groups=G)
+
+        side = _wgrad_side_stream(x.device) if (ctx.needs_input_grad[0] and ctx.needs_input_grad[1]) else None
+        if side is not None:
+            fork = torch.cuda.Event()
+            fork.record(torch.cuda.current_stream(x.device))
+            side.wait_event(fork)
+            with torch.cuda.stream(side):
+                dw = wgrad()
+        if ctx.needs_input_grad[0]:
+            layer._packed(weight, transposed_too=True)
+            dx = C.conv2d_dgrad_strided(dyc, layer._arenaT, cin_g, cout_g, ks, torch.empty_like(x), groups=G)
+        if side is not None:
+            done = torch.cuda.Event()
+            done.record(side)
+            torch.cuda.current_stream(x.device).wait_event(done)
+        elif ctx.needs_input_grad[1]:
+            dw = wgrad()
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            from .layers import channel_sum
             db = torch.empty(Cout, dtype=torch.float32, device=dy.device)
             channel_sum(dyc, 0, Cout, db)
         return dx, dw, db, None

@@ -51,9 +51,11 @@ typedef enum cd_depth_mode {
  * 9: cd_consistency_loss_workspace_init added -- a loss workspace must be initialised once before its first use; cd_copy_segments,
  *    cd_counters_add, cd_zero_bytes, cd_debug_set_layers_mode added;
  * 10: cd_bicubic_fwd / cd_bicubic_bwd / cd_pad_cat_fwd / cd_pad_cat_bwd / cd_crop_act_fwd / cd_crop_act_bwd added -- the monodepth2
- *    decoder and its resizing).
+ *    decoder and its resizing;
+ * 11: cd_conv2d_strided_supported / cd_conv2d_fwd_strided / cd_conv2d_dgrad_strided / cd_conv2d_wgrad_strided / cd_subsample2_fwd /
+ *    cd_subsample2_bwd added -- native stride-2 convolution).
  * The loader (consistent_depth_amd/_native.py) refuses a library whose cd_abi_version() differs from this constant. */
-#define CD_ABI_VERSION 10
+#define CD_ABI_VERSION 11
 int cd_abi_version(void);
 
 /* Batch-statistics buffers (the `stats` arguments below) hold CD_BN_STAT_SLOTS partial copies:
@@ -254,8 +256,8 @@ typedef struct cd_pack_desc {
 } cd_pack_desc;
 int cd_conv2d_pack_weights_table(const void* table_dev, int n, void* stream);
 
-/* y[:, y_coff : y_coff+Cout] = conv2d(act(x[:, x_coff : x_coff+Cin]), w) + bias, stride 1, zero
- * padding (ks-1)/2, ks in {1,3,5,7,11}, at fp32 accuracy: on the BF16 matrix cores from exactly split operands or on the fp32
+/* y[:, y_coff : y_coff+Cout] = conv2d(act(x[:, x_coff : x_coff+Cin]), w) + bias, stride 1 (stride 2: the
+ * cd_conv2d_*_strided family below), zero padding (ks-1)/2, ks in {1,3,5,7,11}, at fp32 accuracy: on the BF16 matrix cores from exactly split operands or on the fp32
  * matrix instruction, by cd_set_conv_arith (below).
  *   act(v) = relu?(v * in_scale[c] + in_shift[c])   when in_scale/in_shift are given (the producer's
  *            BatchNorm-apply [+ReLU] fused into the load), relu only when in_relu and no scale, else v;
@@ -302,6 +304,36 @@ int cd_conv2d_fwd_multi(const cd_conv_desc* descs, int n, int tile_rows, int co_
 int cd_conv2d_wgrad_grouped(const float* x, int x_ctot, int x_coff, int cin_g, const float* dy, int dy_ctot, int dy_coff, int cout_g,
                             int groups, float* dw, int accumulate, float* workspace, size_t workspace_group_stride, int N, int H, int W,
                             int ks, void* stream);
+
+/* Stride-2 convolution, nn.Conv2d(ks, stride = 2, padding = (ks-1)/2): x / dx are [N][*][H][W], y / dy [N][*][Ho][Wo] with
+ * Ho x Wo = ceil(H/2) x ceil(W/2); output pixel (yo, xo) is centred on input pixel (2yo, 2xo); any H, W.  H, W are ALWAYS the extents
+ * of the un-strided side.  Tensors are (pointer, total channels, channel offset) slices and all `groups` run in ONE launch per
+ * pass, as in cd_conv2d_fwd_grouped (groups = 1: a dense convolution).  Split-bf16 arithmetic (modes 1 and 2 of cd_set_conv_arith):
+ * fp32-accurate, no atomics, bit-reproducible.  The filters are the packs the stride-1 entries consume: transposed = 0 of
+ * (cout_g, cin_g, ks) for the forward, transposed = 1 for the input gradient.
+ *   cd_conv2d_strided_supported (host only): 1 when `pass` (0 forward, 1 input gradient, 2 weight gradient) of this geometry has a
+ *     native path: ks = 3 with >= 8 input channels per group through the three entries below; ks = 1 by composing
+ *     cd_subsample2_fwd / _bwd with the stride-1 1x1 entries (the _strided entries themselves take ks = 3 only).  0 for any
+ *     stride but 2, ks = 5, 7, 11 and fewer than 8 input channels (the RGB stems).
+ *   cd_conv2d_fwd_strided: y (+)= conv(x) + bias.        cd_conv2d_dgrad_strided: dx (+)= the input gradient; EVERY element of dx
+ *     is written (zeros where no tap reaches), no zero-stuffed intermediate.       cd_conv2d_wgrad_strided: dw (+)= the weight
+ *     gradient, workspace as cd_conv2d_wgrad_grouped (cd_conv2d_wgrad_workspace_floats per group).
+ * CD_ERR_UNSUPPORTED, nothing launched: stride != 2, a geometry the query rejects, arithmetic mode 0 (an entry never changes
+ * arithmetic silently).  No host synchronisation, no allocation: capturable into a HIP graph. */
+int cd_conv2d_strided_supported(int pass, int ks, int stride, int cin_g, int cout_g);
+int cd_conv2d_fwd_strided(const float* x, int x_ctot, int x_coff, int cin_g, const float* packed_w, size_t packed_group_stride, const float* bias,
+                          float* y, int y_ctot, int y_coff, int cout_g, int groups, int accumulate, int N, int H, int W, int ks, int stride,
+                          void* stream);
+int cd_conv2d_dgrad_strided(const float* dy, int dy_ctot, int dy_coff, int cout_g, const float* packed_wT, size_t packed_group_stride, float* dx,
+                            int dx_ctot, int dx_coff, int cin_g, int groups, int accumulate, int N, int H, int W, int ks, int stride,
+                            void* stream);
+int cd_conv2d_wgrad_strided(const float* x, int x_ctot, int x_coff, int cin_g, const float* dy, int dy_ctot, int dy_coff, int cout_g, int groups,
+                            float* dw, int accumulate, float* workspace, size_t workspace_group_stride, int N, int H, int W, int ks, int stride,
+                            void* stream);
+/* y[N][C][Ho][Wo] = x[:, coff : coff+C, ::2, ::2] of x[N][ctot][H][W], and its adjoint: dx[:, coff : coff+C] = dy at even (row, column),
+ * 0 elsewhere -- the whole [H][W] plane is written in one pass.  The two halves of a 1x1 / 2 convolution around the stride-1 1x1 entries. */
+int cd_subsample2_fwd(const float* x, int ctot, int coff, int C, float* y, int N, int H, int W, void* stream);
+int cd_subsample2_bwd(const float* dy, float* dx, int ctot, int coff, int C, int N, int H, int W, void* stream);
 
 /* Arithmetic of the convolutions (forward, input gradient and weight gradient), process-wide; start-up value from
  * CD_AMD_CONV_ARITH = "split" (2, default) | "split3" (1) | "fp32" (0):
