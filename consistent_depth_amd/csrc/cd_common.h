@@ -16,6 +16,16 @@ constexpr int kBlock = 256;  // 4 waves: one per SIMD of a CU
         if (hipGetLastError() != hipSuccess) return CD_ERR_LAUNCH; \
     } while (0)
 
+// Lets Kernel be launched with up to 160 KB of dynamic LDS (the runtime's default limit is 64 KB); asked once per kernel instantiation.
+template <auto Kernel>
+static inline void allow_full_lds() {
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr_set = true;
+    }
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);

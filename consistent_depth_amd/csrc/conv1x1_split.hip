@@ -15,24 +15,9 @@
 // The order of accumulation is K-step by K-step for every launch: results do not depend on the launch shape.
 #include "cd_common.h"
 #include "conv_split.h"
+#include "split_bf16.h"
 
 namespace cd {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned p1_cvt_pk_bf16(float a, float b) {
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ void p1_split_pair(float a, float b, unsigned& h, unsigned& m, unsigned& l) {
-    h = p1_cvt_pk_bf16(a, b);
-    const float ra = a - __uint_as_float(h << 16), rb = b - __uint_as_float(h & 0xffff0000u);
-    m = p1_cvt_pk_bf16(ra, rb);
-    l = p1_cvt_pk_bf16(ra - __uint_as_float(m << 16), rb - __uint_as_float(m & 0xffff0000u));
-}
 
 // ---------------------------------------------------------------- weight packing
 // [column tile of 32][K-step of 16 channels][split][lane][8 bf16]: element e of lane (n = lane&31, g = lane>>5) = w[tile*32 + n][step*16 + 8g + e]
@@ -51,7 +36,7 @@ __device__ __forceinline__ void pack_1x1_elements(const float* __restrict__ w, u
         if ((unsigned)oc >= (unsigned)oc_n || (unsigned)ic >= (unsigned)ic_n) continue;   // padding stays zero
         const float v = transposed ? w[(size_t)ic * Cin_src + oc] : w[(size_t)oc * Cin_src + ic];
         unsigned h, m, l;
-        p1_split_pair(v, 0.f, h, m, l);
+        split_pair(v, 0.f, h, m, l);
         const size_t base = (((size_t)tile * ksteps + step) * 3) * 512 + (size_t)lane * 8 + e;
         out[base] = (unsigned short)h; out[base + 512] = (unsigned short)m; out[base + 1024] = (unsigned short)l;
     }
@@ -189,25 +174,18 @@ __global__ __launch_bounds__(NW * 64, WPE) void conv1x1_split_kernel(
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
             }
-            u32x4 hh, mm, ll;
-#pragma unroll
-            for (int c2 = 0; c2 < 4; ++c2) {
-                unsigned h, mi, l;
-                p1_split_pair(v[2 * c2], v[2 * c2 + 1], h, mi, l);
-                hh[c2] = h; mm[c2] = mi; ll[c2] = l;
-            }
-            const bf16x8 a[3] = {__builtin_bit_cast(bf16x8, hh), __builtin_bit_cast(bf16x8, mm), __builtin_bit_cast(bf16x8, ll)};
+            bf16x8 a[3];
+            split8(v, a);
             bf16x8 b[NT][3];
 #pragma unroll
             for (int t = 0; t < NT; ++t)
 #pragma unroll
                 for (int sp = 0; sp < 3; ++sp) b[t][sp] = __builtin_bit_cast(bf16x8, s_w[((ks * 3 + sp) * NT + t) * 64 + lane]);
-            constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};   // six products, smallest first, round-robin over the accumulators
 #pragma unroll
-            for (int p = 0; p < 6; ++p)
+            for (int p = 0; p < 6; ++p)   // six products, smallest first (split_bf16.h), round-robin over the accumulators
 #pragma unroll
                 for (int t = 0; t < NT; ++t)
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA[p]], b[t][PB[p]], acc[t], 0, 0, 0);
+                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[SPLIT_PA[p]], b[t][SPLIT_PB[p]], acc[t], 0, 0, 0);
         };
 #pragma unroll 1
         for (int ks = 0; ks < ksteps; ks += DEPTH) {
@@ -288,11 +266,7 @@ template <int NT, int NW, int DEPTH, int WPE>
 static int launch_1x1_t(const float* x, int x_ctot, int x_coff, int Cin, const float* wsplit, const float* bias, const float* in_scale,
                         const float* in_shift, int in_relu, float* y, int y_ctot, int y_coff, int Cout, double* stats, int accumulate, int N,
                         int H, int W, size_t lds, int blocks_per_cu, hipStream_t s) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)conv1x1_split_kernel<NT, NW, DEPTH, WPE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
+    allow_full_lds<conv1x1_split_kernel<NT, NW, DEPTH, WPE>>();
     const int col_tiles = (Cout + 31) / 32, slices = (col_tiles + NT - 1) / NT;
     const int tiles_x = (W + 31) / 32, tiles_total = N * H * tiles_x;
     int nblk = (256 * blocks_per_cu + slices - 1) / slices;          // blocks per slice: fill the chip, every block loads the filter once
@@ -429,25 +403,18 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void conv1x1_split_kc_kernel
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
                 }
-                u32x4 hh, mm, ll;
-#pragma unroll
-                for (int c2 = 0; c2 < 4; ++c2) {
-                    unsigned h, mi, l;
-                    p1_split_pair(v[2 * c2], v[2 * c2 + 1], h, mi, l);
-                    hh[c2] = h; mm[c2] = mi; ll[c2] = l;
-                }
-                const bf16x8 a[3] = {__builtin_bit_cast(bf16x8, hh), __builtin_bit_cast(bf16x8, mm), __builtin_bit_cast(bf16x8, ll)};
+                bf16x8 a[3];
+                split8(v, a);
                 bf16x8 b[NT][3];
 #pragma unroll
                 for (int t = 0; t < NT; ++t)
 #pragma unroll
                     for (int sp = 0; sp < 3; ++sp) b[t][sp] = __builtin_bit_cast(bf16x8, sw[((j * 3 + sp) * NT + t) * 64 + lane]);
-                constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};   // six products, smallest first (as above)
 #pragma unroll
-                for (int p = 0; p < 6; ++p)
+                for (int p = 0; p < 6; ++p)   // (as above)
 #pragma unroll
                     for (int t = 0; t < NT; ++t)
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA[p]], b[t][PB[p]], acc[t], 0, 0, 0);
+                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[SPLIT_PA[p]], b[t][SPLIT_PB[p]], acc[t], 0, 0, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -516,11 +483,7 @@ static int launch_1x1_kc_t(const float* x, int x_ctot, int x_coff, int Cin, cons
                            int H, int W, hipStream_t s) {
     const int ksteps = ((Cin + 15) / 16 + 3) / 4 * 4;
     const size_t lds = (size_t)2 * 4 * 3 * NT * 1024 + (size_t)2 * ksteps * 16 * 4;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)conv1x1_split_kc_kernel<NT, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
+    allow_full_lds<conv1x1_split_kc_kernel<NT, NW>>();
     const int col_tiles = (Cout + 31) / 32, slices = (col_tiles + NT - 1) / NT;
     const int P_total = N * H * W, tiles_total = (P_total + 31) / 32, ngroups = (tiles_total + NW - 1) / NW;
     hipLaunchKernelGGL((conv1x1_split_kc_kernel<NT, NW>), dim3((unsigned)((ngroups + 7) / 8) * 8u * (unsigned)slices), dim3(NW * 64), lds, s, x, x_ctot,

@@ -402,11 +402,7 @@ static int launch_conv_t(const float* x, int x_ctot, int x_coff, int Cin, const 
     const int pack_cob = pack_cot * 16, groups = (Cout + pack_cob - 1) / pack_cob;
     const int n_chunks = (Cin + Cfg::CI_CHUNK - 1) / Cfg::CI_CHUNK;
     const size_t lds = sizeof(float) * ((size_t)Cfg::CI_CHUNK * Cfg::PS + (size_t)KS * KS * Cfg::CI_CHUNK * COBP + 2 * (size_t)n_chunks * Cfg::CI_CHUNK);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)conv_fwd_kernel<KS, CO_T, TYP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
+    allow_full_lds<conv_fwd_kernel<KS, CO_T, TYP>>();
     if (lds > 160 * 1024 || lds < sizeof(double) * 8 * COB) return CD_ERR_UNSUPPORTED;   // (the statistics reduction reuses 8*COB doubles)
     const int slices = (Cout + COB - 1) / COB;   // channel slices with at least one live channel
     const int tiles_img = tiles_x * tiles_y, tiles_total = tiles_img * N, chunk = (tiles_total + 7) / 8;

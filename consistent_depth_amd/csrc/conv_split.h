@@ -34,6 +34,19 @@ __host__ __device__ inline size_t fp32_packed_floats(int OC, int IC, int ks) {
     return (size_t)groups * chunks * ks * ks * ci_chunk * cobp;
 }
 
+// The split-bf16 packed filter of a k x k convolution (k in {3, 5, 7, 11}; packed by conv_split.hip, read by its kernels and -- at
+// k = 3 -- by the stride-2 kernels of conv_strided.hip), appended to the fp32 layout:
+//     [column tile][ci chunk of 8][step][hi | mid | lo][lane][8 bf16]
+// A step is two consecutive taps of the flattened (ky', kx) index (lane >> 5 selects the tap) and SPLIT_STEP_UNITS 16-byte units
+// long: one per lane and split, in the B-fragment order of v_mfma_f32_32x32x16_bf16.  A column tile is 32 output channels -- or,
+// when the convolution has at most 16 of them, 16 channels x DY = 2 output rows, the second row's filter shifted down by one tap
+// row (taps over ks + 1 rows, zero weights where the shift leaves the filter).
+__host__ __device__ constexpr int split_dy(int OC) { return OC <= 16 ? 2 : 1; }                  // output rows per M-tile
+__host__ __device__ constexpr int split_taps(int ks, int dy) { return (ks + dy - 1) * ks; }      // flattened (ky', kx), ky' over ks + dy - 1 rows
+__host__ __device__ constexpr int split_steps(int ks, int dy) { return (split_taps(ks, dy) + 1) / 2; }
+__host__ __device__ constexpr int split_ntiles(int OC) { return split_dy(OC) == 2 ? 1 : (OC + 31) / 32; }
+constexpr int SPLIT_STEP_UNITS = 3 * 64;
+
 // 1x1 filters (conv1x1_split.hip; forward / input gradient only): more than 16 output and at least 32 input channels, and the
 // block's filter slice (64 output channels x all input channels x 6 bytes) must fit the LDS
 // (IC <= 384: the filter slice stays in LDS, conv1x1_split_kernel; up to 2048 since round 6: the chunked kernel conv1x1_split_kc_kernel)

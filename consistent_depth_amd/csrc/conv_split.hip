@@ -31,6 +31,7 @@
 // Fusions (input affine/ReLU, bias, accumulate, BatchNorm statistics) are those of conv_mfma.hip.
 #include "cd_common.h"
 #include "conv_split.h"
+#include "split_bf16.h"
 
 #ifndef CD_SP_DBG        // measurement builds (tools/exp/build_variants.sh): 1 = no MFMA phase, 2 = no staging (profiles/conv_phases_r03.txt), 4 = staging without its global loads
 #define CD_SP_DBG 0
@@ -38,36 +39,7 @@
 
 namespace cd {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int SP_TX = 32;
-
-// two fp32 -> packed bf16 pair (round to nearest even), low half = a
-__device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b) {
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float bf16_lo(unsigned p) { return __uint_as_float(p << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned p) { return __uint_as_float(p & 0xffff0000u); }
-
-// (a, b) -> packed pairs of the three split terms
-__device__ __forceinline__ void split_pair(float a, float b, unsigned& h, unsigned& m, unsigned& l) {
-    h = cvt_pk_bf16(a, b);
-    const float ra = a - bf16_lo(h), rb = b - bf16_hi(h);
-    m = cvt_pk_bf16(ra, rb);
-    l = cvt_pk_bf16(ra - bf16_lo(m), rb - bf16_hi(m));
-}
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// DY = output rows per M-tile (2 when the convolution has <= 16 output channels)
-__host__ __device__ constexpr int split_dy(int OC) { return OC <= 16 ? 2 : 1; }
-__host__ __device__ constexpr int split_taps(int ks, int dy) { return (ks + dy - 1) * ks; }      // flattened (ky', kx), ky' over KS + DY - 1 rows
-__host__ __device__ constexpr int split_steps(int ks, int dy) { return (split_taps(ks, dy) + 1) / 2; }
-__host__ __device__ constexpr int split_ntiles(int OC) { return split_dy(OC) == 2 ? 1 : (OC + 31) / 32; }
 
 template <int KS, int TY_, int DY> struct SplitCfg {
     static constexpr int TY = TY_;
@@ -80,7 +52,7 @@ template <int KS, int TY_, int DY> struct SplitCfg {
 };
 
 // ---------------------------------------------------------------- weight packing (split layout)
-// [column tile][ci chunk of 8][step][split][lane][8 bf16]; element e of lane (n = lane&31, g = lane>>5) is
+// The layout of conv_split.h: [column tile][ci chunk of 8][step][split][lane][8 bf16]; element e of lane (n = lane&31, g = lane>>5) is
 // w[column n][chunk*8 + e][tap 2*step + g]; column n = output channel tile*32 + n, or (OC <= 16) channel n&15 of output row
 // dy = n>>4, whose filter row is ky' - dy.
 __device__ __forceinline__ void pack_split_elements(const float* __restrict__ w, unsigned short* __restrict__ out, int Cout_src, int Cin_src,
@@ -206,7 +178,7 @@ __device__ __forceinline__ void conv_fwd_split_block(const SplitArgs& a, const i
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         const int gt = slice * NT + t;
-        wt[t] = wsp + (size_t)(gt < pack_tiles ? gt : 0) * n_chunks * KSTEPS * 192 + lane;
+        wt[t] = wsp + (size_t)(gt < pack_tiles ? gt : 0) * n_chunks * KSTEPS * SPLIT_STEP_UNITS + lane;
     }
     const int steps_total = n_chunks * KSTEPS;
     // weight fragments: two register buffers used alternately (explicitly -- a "next = load; ...; cur = next" rotation was folded
@@ -217,7 +189,7 @@ __device__ __forceinline__ void conv_fwd_split_block(const SplitArgs& a, const i
         for (int t = 0; t < NT; ++t)
 #pragma unroll
             for (int sp = 0; sp < 3; ++sp) {
-                const u32x4 v = wt[t][(size_t)(lin < steps_total ? lin : steps_total - 1) * 192 + sp * 64];   // (always a load: no branch)
+                const u32x4 v = wt[t][(size_t)(lin < steps_total ? lin : steps_total - 1) * SPLIT_STEP_UNITS + sp * 64];   // (always a load: no branch)
                 dst[t][sp] = __builtin_bit_cast(bf16x8, v);
             }
     };
@@ -347,7 +319,6 @@ __device__ __forceinline__ void conv_fwd_split_block(const SplitArgs& a, const i
             const int ky = tap / KS, kx = tap - ky * KS;
             // a padded tap carries zero weights: any valid slot
             const int slot0 = abase + (chunk - round * CGS) * 3 * PLANE + ((tap < TAPS) ? ky * RSP + kx : 0);
-            constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};   // six products, smallest first
 #pragma unroll
             for (int mg = 0; mg < MB; mg += MG) {
                 bf16x8 a[MG][3];
@@ -359,12 +330,12 @@ __device__ __forceinline__ void conv_fwd_split_block(const SplitArgs& a, const i
                     a[m][2] = __builtin_bit_cast(bf16x8, s_in[2 * PLANE + slot]);
                 }
 #pragma unroll
-                for (int p = 0; p < 6; ++p)   // round-robin over the accumulators: a dependent MFMA never follows its producer
+                for (int p = 0; p < 6; ++p)   // six products, smallest first (split_bf16.h), round-robin over the accumulators: a dependent MFMA never follows its producer
 #pragma unroll
                     for (int m = 0; m < MG; ++m)
 #pragma unroll
                         for (int t = 0; t < NT; ++t)
-                            acc[mg + m][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][PA[p]], bcur[t][PB[p]], acc[mg + m][t], 0, 0, 0);
+                            acc[mg + m][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][SPLIT_PA[p]], bcur[t][SPLIT_PB[p]], acc[mg + m][t], 0, 0, 0);
             }
         };
         if (CD_SP_DBG & 1) { lin += ((lin_end - lin + 3) / 4) * 4; continue; }
@@ -533,11 +504,7 @@ static int launch_split_t(const float* x, int x_ctot, int x_coff, int Cin, const
     const int tiles_x = (W + SP_TX - 1) / SP_TX, tiles_y = (H + Cfg::TY - 1) / Cfg::TY;
     const size_t img = CGS * Cfg::LDS + split_aff_bytes(Cin);      // the LDS images + the producer's scale / shift table behind them
     const size_t lds = img > SPLIT_REDUCE_LDS ? img : SPLIT_REDUCE_LDS;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)conv_fwd_split_kernel<KS, NT, TYP, DY, CGS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
+    allow_full_lds<conv_fwd_split_kernel<KS, NT, TYP, DY, CGS>>();
     if (lds > 160 * 1024) return CD_ERR_UNSUPPORTED;
     const int pack_tiles = split_ntiles(Cout), slices = (pack_tiles + NT - 1) / NT;
     const int tiles_img = tiles_x * tiles_y, tiles_total = tiles_img * N, chunk_tiles = (tiles_total + 7) / 8;
@@ -571,11 +538,7 @@ static int launch_split_multi_t(const SplitConv* c, int n, int N, int H, int W, 
     }
     for (int i = n; i < kSplitMultiMax; ++i) { m.b[i] = m.b[0]; m.ks[i] = m.ks[0]; }
     if (lds > 160 * 1024) return CD_ERR_UNSUPPORTED;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)conv_fwd_split_multi_kernel<NT, TYP, DY, CGS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
+    allow_full_lds<conv_fwd_split_multi_kernel<NT, TYP, DY, CGS>>();
     hipLaunchKernelGGL((conv_fwd_split_multi_kernel<NT, TYP, DY, CGS>), dim3((unsigned)chunk_tiles * 8u * (unsigned)slices, (unsigned)n), dim3(kBlock), lds, s, m);
     return hipGetLastError() == hipSuccess ? CD_OK : CD_ERR_LAUNCH;
 }
@@ -606,7 +569,7 @@ int split_column_tiles(int OC) { return split_ntiles(OC); }
 size_t split_packed_floats(int OC, int IC, int ks) {
     if (!split_supported(ks)) return 0;
     const size_t chunks = ((size_t)IC + 7) / 8;
-    return (size_t)split_ntiles(OC) * chunks * split_steps(ks, split_dy(OC)) * 3 * 64 * 4;   // 16 bytes = 4 floats per lane per split
+    return (size_t)split_ntiles(OC) * chunks * split_steps(ks, split_dy(OC)) * SPLIT_STEP_UNITS * 4;   // 16-byte units = 4 floats each
 }
 
 int launch_pack_split(const float* w, int Cout, int Cin, int ks, int transposed, float* packed_split, hipStream_t s) {

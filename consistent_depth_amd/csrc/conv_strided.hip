@@ -27,33 +27,13 @@
 #include "cd_common.h"
 #include "conv_split.h"
 #include "conv_strided.h"
+#include "split_bf16.h"
 
 namespace cd {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned s2_cvt_pk_bf16(float a, float b) {
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-// (a, b) -> packed pairs of the three split terms (as conv_split.hip)
-__device__ __forceinline__ void s2_split_pair(float a, float b, unsigned& h, unsigned& m, unsigned& l) {
-    h = s2_cvt_pk_bf16(a, b);
-    const float ra = a - __uint_as_float(h << 16), rb = b - __uint_as_float(h & 0xffff0000u);
-    m = s2_cvt_pk_bf16(ra, rb);
-    l = s2_cvt_pk_bf16(ra - __uint_as_float(m << 16), rb - __uint_as_float(m & 0xffff0000u));
-}
-
-// the stride-1 split layout of a 3x3 filter (conv_split.hip): <= 16 output channels are packed as 16 channels x 2 output rows
-// (taps over 4 filter rows; columns 0..15 hold the unshifted filter), else 32 channels per column tile
-__host__ __device__ constexpr int s2_pack_dy(int OC) { return OC <= 16 ? 2 : 1; }
-__host__ __device__ constexpr int s2_pack_steps(int dyl) { return ((3 + dyl - 1) * 3 + 1) / 2; }
-static inline int s2_pack_tiles(int OC) { return s2_pack_dy(OC) == 2 ? 1 : (OC + 31) / 32; }
+// The filters are the stride-1 split packs of a 3x3 convolution, whose geometry conv_split.h owns (split_dy, split_steps,
+// split_ntiles, SPLIT_STEP_UNITS): with <= 16 output channels a column tile holds 16 channels x 2 output rows (taps over 4 filter
+// rows), of which only columns 0..15 -- the unshifted filter -- are used here.
 
 // One forward / input-gradient launch.  src: the tensor the reduction runs over (x, or dy), dst: the result (y, or dx);
 // H x W: the un-strided extents (x / dx), Ho x Wo the strided ones (y / dy).
@@ -63,15 +43,13 @@ struct S2Args {
     size_t g_w;
 };
 
-constexpr int PA6[6] = {2, 0, 1, 1, 0, 0}, PB6[6] = {0, 2, 1, 0, 1, 0};   // six products, smallest first (conv_split.hip)
-
 // ---------------------------------------------------------------- forward
 constexpr int S2F_TY = 8, S2F_ROWS = 2 * S2F_TY + 1, S2F_PW = 36, S2F_RS = 2 * S2F_PW, S2F_PLANE = S2F_ROWS * S2F_RS;
 constexpr size_t S2F_LDS = (size_t)3 * S2F_PLANE * 16;
 
 template <int DYL>
 __global__ __launch_bounds__(kBlock, 2) void conv_s2_fwd_kernel(const S2Args a) {
-    constexpr int TY = S2F_TY, ROWS = S2F_ROWS, PW = S2F_PW, RS = S2F_RS, PLANE = S2F_PLANE, KSTEPS = s2_pack_steps(DYL);
+    constexpr int TY = S2F_TY, ROWS = S2F_ROWS, PW = S2F_PW, RS = S2F_RS, PLANE = S2F_PLANE, KSTEPS = split_steps(3, DYL);
     constexpr int QUADS = RS / 4, UNITS = ROWS * QUADS;
     extern __shared__ __attribute__((aligned(16))) unsigned char s2_smem[];
     u32x4* s_in = reinterpret_cast<u32x4*>(s2_smem);   // [3 splits][ROWS][parity][PW] 16-byte slots (8 bf16 channels of one pixel)
@@ -88,7 +66,7 @@ __global__ __launch_bounds__(kBlock, 2) void conv_s2_fwd_kernel(const S2Args a) 
     const float* xin = a.src + ((size_t)n * a.s_ctot + a.s_coff + grp * a.g_s) * HW;
     const int n_chunks = (IC + 7) / 8;
     const bool vec_in = (W & 3) == 0;
-    const u32x4* wt = a.wsp + (size_t)grp * a.g_w + (size_t)ct * n_chunks * KSTEPS * 192 + lane;
+    const u32x4* wt = a.wsp + (size_t)grp * a.g_w + (size_t)ct * n_chunks * KSTEPS * SPLIT_STEP_UNITS + lane;
 
     f32x16 acc[2];
 #pragma unroll
@@ -111,7 +89,7 @@ __global__ __launch_bounds__(kBlock, 2) void conv_s2_fwd_kernel(const S2Args a) 
 #pragma unroll
         for (int st = 0; st < KSTEPS; ++st)
 #pragma unroll
-            for (int sp = 0; sp < 3; ++sp) b[st][sp] = __builtin_bit_cast(bf16x8, wt[((size_t)chunk * KSTEPS + st) * 192 + sp * 64]);
+            for (int sp = 0; sp < 3; ++sp) b[st][sp] = __builtin_bit_cast(bf16x8, wt[((size_t)chunk * KSTEPS + st) * SPLIT_STEP_UNITS + sp * 64]);
         __syncthreads();   // the previous chunk's tile is consumed
         for (int u = threadIdx.x; u < UNITS; u += kBlock) {
             const int r = u / QUADS, q4 = (u - r * QUADS) * 4;
@@ -149,7 +127,7 @@ __global__ __launch_bounds__(kBlock, 2) void conv_s2_fwd_kernel(const S2Args a) 
                 for (int c2 = 0; c2 < 4; ++c2) {
                     const unsigned k0 = keep[p] & (chunk * 8 + 2 * c2 < IC ? 0xffffffffu : 0u), k1 = keep[p] & (chunk * 8 + 2 * c2 + 1 < IC ? 0xffffffffu : 0u);
                     unsigned h, m, l;   // zero padding (pixels and channels) stays an exact zero
-                    s2_split_pair(__uint_as_float(__float_as_uint(v[2 * c2][p]) & k0), __uint_as_float(__float_as_uint(v[2 * c2 + 1][p]) & k1), h, m, l);
+                    split_pair(__uint_as_float(__float_as_uint(v[2 * c2][p]) & k0), __uint_as_float(__float_as_uint(v[2 * c2 + 1][p]) & k1), h, m, l);
                     hh[c2] = h; mm[c2] = m; ll[c2] = l;
                 }
                 const int c = q4 + p, slot = r * RS + (c & 1) * PW + (c >> 1);
@@ -170,7 +148,7 @@ __global__ __launch_bounds__(kBlock, 2) void conv_s2_fwd_kernel(const S2Args a) 
 #pragma unroll
             for (int p = 0; p < 6; ++p)
 #pragma unroll
-                for (int m = 0; m < 2; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[m][PA6[p]], b[st][PB6[p]], acc[m], 0, 0, 0);
+                for (int m = 0; m < 2; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[m][SPLIT_PA[p]], b[st][SPLIT_PB[p]], acc[m], 0, 0, 0);
         }
     }
 
@@ -216,7 +194,7 @@ __host__ __device__ constexpr int s2d_off(int t, int py, int px) { return ((py +
 
 template <int DYL>
 __global__ __launch_bounds__(kBlock, 2) void conv_s2_dgrad_kernel(const S2Args a) {
-    constexpr int TA = S2D_TA, ROWS = S2D_ROWS, RS = S2D_RS, PLANE = S2D_PLANE, CG = S2D_CG, KSTEPS = s2_pack_steps(DYL), LIVE_STEPS = 5;
+    constexpr int TA = S2D_TA, ROWS = S2D_ROWS, RS = S2D_RS, PLANE = S2D_PLANE, CG = S2D_CG, KSTEPS = split_steps(3, DYL), LIVE_STEPS = 5;
     constexpr int QUADS = RS / 4, UNITS = ROWS * QUADS;
     extern __shared__ __attribute__((aligned(16))) unsigned char s2_smem[];
     u32x4* s_in = reinterpret_cast<u32x4*>(s2_smem);   // [CG chunks][3 splits][ROWS][RS] slots + the zero slot
@@ -233,7 +211,7 @@ __global__ __launch_bounds__(kBlock, 2) void conv_s2_dgrad_kernel(const S2Args a
     const float* din = a.src + ((size_t)n * a.s_ctot + a.s_coff + grp * a.g_s) * HWo;
     const int n_chunks = (IC + 7) / 8;
     const bool vec_in = (Wo & 3) == 0;
-    const u32x4* wt = a.wsp + (size_t)grp * a.g_w + (size_t)ct * n_chunks * KSTEPS * 192 + lane;
+    const u32x4* wt = a.wsp + (size_t)grp * a.g_w + (size_t)ct * n_chunks * KSTEPS * SPLIT_STEP_UNITS + lane;
     if (threadIdx.x == 0) s_in[S2D_ZERO] = u32x4{0u, 0u, 0u, 0u};   // (visible after the first barrier)
 
     f32x16 acc[2][2];   // [py][px] of this wave's dx row pair 2 (A0 + wid) + py
@@ -285,7 +263,7 @@ __global__ __launch_bounds__(kBlock, 2) void conv_s2_dgrad_kernel(const S2Args a
                 for (int c2 = 0; c2 < 4; ++c2) {
                     const unsigned k0 = keep[p] & (chunk * 8 + 2 * c2 < IC ? 0xffffffffu : 0u), k1 = keep[p] & (chunk * 8 + 2 * c2 + 1 < IC ? 0xffffffffu : 0u);
                     unsigned h, m, l;
-                    s2_split_pair(__uint_as_float(__float_as_uint(v[2 * c2][p]) & k0), __uint_as_float(__float_as_uint(v[2 * c2 + 1][p]) & k1), h, m, l);
+                    split_pair(__uint_as_float(__float_as_uint(v[2 * c2][p]) & k0), __uint_as_float(__float_as_uint(v[2 * c2 + 1][p]) & k1), h, m, l);
                     hh[c2] = h; mm[c2] = m; ll[c2] = l;
                 }
                 const int slot = cg * 3 * PLANE + r * RS + q4 + p;
@@ -301,7 +279,7 @@ __global__ __launch_bounds__(kBlock, 2) void conv_s2_dgrad_kernel(const S2Args a
 #pragma unroll
             for (int st = 0; st < LIVE_STEPS; ++st)
 #pragma unroll
-                for (int sp = 0; sp < 3; ++sp) b[st][sp] = __builtin_bit_cast(bf16x8, wt[((size_t)chunk * KSTEPS + st) * 192 + sp * 64]);
+                for (int sp = 0; sp < 3; ++sp) b[st][sp] = __builtin_bit_cast(bf16x8, wt[((size_t)chunk * KSTEPS + st) * SPLIT_STEP_UNITS + sp * 64]);
             const int img = cg * 3 * PLANE + abase;
 #pragma unroll
             for (int st = 0; st < LIVE_STEPS; ++st)
@@ -319,7 +297,7 @@ __global__ __launch_bounds__(kBlock, 2) void conv_s2_dgrad_kernel(const S2Args a
                         for (int sp = 0; sp < 3; ++sp) av[sp] = __builtin_bit_cast(bf16x8, s_in[lv ? slot + sp * PLANE : S2D_ZERO]);
 #pragma unroll
                         for (int p = 0; p < 6; ++p)
-                            acc[py][px] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[PA6[p]], b[st][PB6[p]], acc[py][px], 0, 0, 0);
+                            acc[py][px] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[SPLIT_PA[p]], b[st][SPLIT_PB[p]], acc[py][px], 0, 0, 0);
                     }
         }
     }
@@ -361,13 +339,9 @@ __global__ __launch_bounds__(kBlock, 2) void conv_s2_dgrad_kernel(const S2Args a
 
 template <int DYL, bool DGRAD>
 static int launch_s2(const S2Args& a, int N, int tiles_c, int groups, hipStream_t s) {
-    static bool attr_set = false;
-    const void* fn = DGRAD ? (const void*)conv_s2_dgrad_kernel<DYL> : (const void*)conv_s2_fwd_kernel<DYL>;
     const size_t lds = DGRAD ? S2D_LDS : S2F_LDS;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
+    if (DGRAD) allow_full_lds<conv_s2_dgrad_kernel<DYL>>();
+    else allow_full_lds<conv_s2_fwd_kernel<DYL>>();
     const long long blocks = (long long)N * a.tiles_x * a.tiles_y;
     if (blocks > 0x7fffffffLL || tiles_c > 65535 || groups > 65535) return CD_ERR_UNSUPPORTED;
     const dim3 grid((unsigned)blocks, (unsigned)tiles_c, (unsigned)groups);
@@ -442,8 +416,8 @@ __global__ __launch_bounds__(kBlock, 2) void conv_s2_wgrad_kernel(const S2WArgs 
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) {   // plane pl holds columns 2xo - 1 + pl
                 unsigned h0, m0, l0, h1, m1, l1;
-                s2_split_pair(v[pl], v[pl + 2], h0, m0, l0);
-                s2_split_pair(v[pl + 4], v[pl + 6], h1, m1, l1);
+                split_pair(v[pl], v[pl + 2], h0, m0, l0);
+                split_pair(v[pl + 4], v[pl + 6], h1, m1, l1);
                 *reinterpret_cast<u32x2*>(d + pl * 16) = u32x2{h0, h1};
                 *reinterpret_cast<u32x2*>(d + pl * 16 + SPX) = u32x2{m0, m1};
                 *reinterpret_cast<u32x2*>(d + pl * 16 + 2 * SPX) = u32x2{l0, l1};
@@ -469,8 +443,8 @@ __global__ __launch_bounds__(kBlock, 2) void conv_s2_wgrad_kernel(const S2WArgs 
                 }
             }
             unsigned h0, m0, l0, h1, m1, l1;
-            s2_split_pair(v[0], v[1], h0, m0, l0);
-            s2_split_pair(v[2], v[3], h1, m1, l1);
+            split_pair(v[0], v[1], h0, m0, l0);
+            split_pair(v[2], v[3], h1, m1, l1);
             unsigned* d = s_dy + c * DCS + r * 16 + 2 * q;
             *reinterpret_cast<u32x2*>(d) = u32x2{h0, h1};
             *reinterpret_cast<u32x2*>(d + SPD) = u32x2{m0, m1};
@@ -496,7 +470,7 @@ __global__ __launch_bounds__(kBlock, 2) void conv_s2_wgrad_kernel(const S2WArgs 
             for (int p = 0; p < 6; ++p)      // all nine taps between two products of one accumulator
 #pragma unroll
                 for (int t = 0; t < 9; ++t)
-                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[PA6[p]], bv[t / 3][PB6[p]][t % 3], acc[t], 0, 0, 0);
+                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[SPLIT_PA[p]], bv[t / 3][SPLIT_PB[p]][t % 3], acc[t], 0, 0, 0);
         }
     }
 
@@ -598,8 +572,8 @@ int cd_conv2d_fwd_strided(const float* x, int x_ctot, int x_coff, int cin_g, con
     a.H = H; a.W = W; a.Ho = (H + 1) / 2; a.Wo = (W + 1) / 2;
     a.tiles_x = (a.Wo + 31) / 32; a.tiles_y = (a.Ho + cd::S2F_TY - 1) / cd::S2F_TY;
     a.g_s = groups > 1 ? cin_g : 0; a.g_d = groups > 1 ? cout_g : 0; a.g_w = groups > 1 ? packed_group_stride / 4 : 0;
-    if (cd::s2_pack_dy(cout_g) == 2) return cd::launch_s2<2, false>(a, N, 1, groups, (hipStream_t)stream);
-    return cd::launch_s2<1, false>(a, N, cd::s2_pack_tiles(cout_g), groups, (hipStream_t)stream);
+    if (cd::split_dy(cout_g) == 2) return cd::launch_s2<2, false>(a, N, 1, groups, (hipStream_t)stream);
+    return cd::launch_s2<1, false>(a, N, cd::split_ntiles(cout_g), groups, (hipStream_t)stream);
 }
 
 int cd_conv2d_dgrad_strided(const float* dy, int dy_ctot, int dy_coff, int cout_g, const float* packed_wT, size_t packed_group_stride, float* dx,
@@ -614,8 +588,8 @@ int cd_conv2d_dgrad_strided(const float* dy, int dy_ctot, int dy_coff, int cout_
     a.H = H; a.W = W; a.Ho = (H + 1) / 2; a.Wo = (W + 1) / 2;
     a.tiles_x = (a.Wo + 31) / 32; a.tiles_y = (a.Ho + cd::S2D_TA - 1) / cd::S2D_TA;
     a.g_s = groups > 1 ? cout_g : 0; a.g_d = groups > 1 ? cin_g : 0; a.g_w = groups > 1 ? packed_group_stride / 4 : 0;
-    if (cd::s2_pack_dy(cin_g) == 2) return cd::launch_s2<2, true>(a, N, 1, groups, (hipStream_t)stream);
-    return cd::launch_s2<1, true>(a, N, cd::s2_pack_tiles(cin_g), groups, (hipStream_t)stream);
+    if (cd::split_dy(cin_g) == 2) return cd::launch_s2<2, true>(a, N, 1, groups, (hipStream_t)stream);
+    return cd::launch_s2<1, true>(a, N, cd::split_ntiles(cin_g), groups, (hipStream_t)stream);
 }
 
 int cd_conv2d_wgrad_strided(const float* x, int x_ctot, int x_coff, int cin_g, const float* dy, int dy_ctot, int dy_coff, int cout_g, int groups,
@@ -641,11 +615,7 @@ int cd_conv2d_wgrad_strided(const float* x, int x_ctot, int x_coff, int cin_g, c
     if (splits > max_splits) splits = max_splits;
     if (splits > items) splits = items;
     if (splits < 1) splits = 1;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)cd::conv_s2_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
+    cd::allow_full_lds<cd::conv_s2_wgrad_kernel>();
     hipLaunchKernelGGL(cd::conv_s2_wgrad_kernel, dim3((unsigned)splits, (unsigned)cigs, (unsigned)(a.zpg * groups)), dim3(cd::kBlock), cd::S2W_LDS,
                        (hipStream_t)stream, a);
     CD_CHECK_LAUNCH();

@@ -530,11 +530,7 @@ static int launch_wgrad_t(const float* x, int x_ctot, int x_coff, int Cin, const
     constexpr int per_cu = (CO_T + CI_T > 16) ? 1 : 2;
     const int splits = wgrad_splits(cogs * cigs, per_cu, items);
     const size_t lds = sizeof(float) * ((size_t)COB * Cfg::PS_DY + (size_t)CIB * Cfg::PS_IN);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)conv_wgrad_kernel<KS, CO_T, CI_T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
+    allow_full_lds<conv_wgrad_kernel<KS, CO_T, CI_T>>();
     if (lds > 160 * 1024) return CD_ERR_UNSUPPORTED;
     hipLaunchKernelGGL((conv_wgrad_kernel<KS, CO_T, CI_T>), dim3(splits, cigs, cogs), dim3(kBlock), lds, s, x, x_ctot, x_coff,
                        Cin, in_scale, in_shift, in_relu, dy, dy_ctot, dy_coff, Cout, packed, N, H, W, tiles_x, tiles_y, g_wgrad_dbg);

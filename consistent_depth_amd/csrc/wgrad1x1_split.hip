@@ -13,32 +13,9 @@
 // All loads are unconditional (clamped channel, masked with an AND): see conv1x1_split.hip for why.
 #include "cd_common.h"
 #include "wgrad_split.h"
+#include "split_bf16.h"
 
 namespace cd {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned w1_cvt_pk_bf16(float a, float b) {
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-// 8 fp32 -> three bf16x8 fragments (hi, mid, lo)
-__device__ __forceinline__ void w1_split8(const float (&v)[8], bf16x8 (&f)[3]) {
-    u32x4 hh, mm, ll;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const float a = v[2 * c], b = v[2 * c + 1];
-        const unsigned h = w1_cvt_pk_bf16(a, b);
-        const float ra = a - __uint_as_float(h << 16), rb = b - __uint_as_float(h & 0xffff0000u);
-        const unsigned m = w1_cvt_pk_bf16(ra, rb);
-        const unsigned l = w1_cvt_pk_bf16(ra - __uint_as_float(m << 16), rb - __uint_as_float(m & 0xffff0000u));
-        hh[c] = h; mm[c] = m; ll[c] = l;
-    }
-    f[0] = __builtin_bit_cast(bf16x8, hh); f[1] = __builtin_bit_cast(bf16x8, mm); f[2] = __builtin_bit_cast(bf16x8, ll);
-}
 
 constexpr int W1_CO_T = WGRAD1X1_COB / 32, W1_CI_T = WGRAD1X1_CIB / 32;   // accumulator tiles of a patch: 2 x 4
 
@@ -114,9 +91,8 @@ __global__ __launch_bounds__(kBlock, 2) void wgrad1x1_split_kernel(
             float v[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = __uint_as_float(__float_as_uint(ra[buf][t][e]) & a_keep[t]);
-            w1_split8(v, fa[t]);
+            split8(v, fa[t]);
         }
-        constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};   // six products, smallest first
 #pragma unroll
         for (int t = 0; t < W1_CI_T; ++t) {
             float v[8];
@@ -128,12 +104,12 @@ __global__ __launch_bounds__(kBlock, 2) void wgrad1x1_split_kernel(
                 v[e] = __uint_as_float(__float_as_uint(u) & b_keep[t]);
             }
             bf16x8 fb[3];
-            w1_split8(v, fb);
+            split8(v, fb);
 #pragma unroll
-            for (int p = 0; p < 6; ++p)
+            for (int p = 0; p < 6; ++p)   // six products, smallest first (split_bf16.h)
 #pragma unroll
                 for (int a = 0; a < W1_CO_T; ++a)
-                    acc[a][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[a][PA[p]], fb[PB[p]], acc[a][t], 0, 0, 0);
+                    acc[a][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[a][SPLIT_PA[p]], fb[SPLIT_PB[p]], acc[a][t], 0, 0, 0);
         }
     };
     if (s0 < s1) {

@@ -18,6 +18,7 @@
 // bit-reproducible.
 #include "cd_common.h"
 #include "wgrad_split.h"
+#include "split_bf16.h"
 
 #ifndef CD_WGRAD_AHEAD11   // 1: fetch the next tile ahead at k = 11 too (27 spilled registers: measured slower than all-loads-at-once)
 #define CD_WGRAD_AHEAD11 0
@@ -28,31 +29,15 @@
 
 namespace cd {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned ws_cvt_pk_bf16(float a, float b) {
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-// (a, b) -> packed pairs of the three split terms (as conv_split.hip)
-__device__ __forceinline__ void ws_split_pair(float a, float b, unsigned& h, unsigned& m, unsigned& l) {
-    h = ws_cvt_pk_bf16(a, b);
-    const float ra = a - __uint_as_float(h << 16), rb = b - __uint_as_float(h & 0xffff0000u);
-    m = ws_cvt_pk_bf16(ra, rb);
-    l = ws_cvt_pk_bf16(ra - __uint_as_float(m << 16), rb - __uint_as_float(m & 0xffff0000u));
-}
-
 // One wave's share of a staged tile: output-channel sub-tile WV / WPS, taps [(WV % WPS) * TPW, + TPW) of the flattened index
 // (13 at k = 7, 16 at k = 11: they span two or three filter rows).  Per output row y and B split the windows of ALL the wave's filter
 // rows are loaded (three ds_read_b128 = 12 registers each) and the MFMAs walk over all the wave's taps before the next dY split
 // revisits an accumulator: v_mfma_f32_16x16x32_bf16 needs many independent accumulators in flight (profiles/mfma_rate_exp_r02.txt:
 // 55 % of its rate with 4-8, the full rate with 16); the round-robin over the 5-11 taps of ONE filter row (rounds 2/3) ran the MFMA
 // phase at ~60 % even with the operand work and the LDS reads removed (profiles/wgrad_phases_r03.txt).  Every accumulator still
-// receives its six products per row in the same order -- lo x hi; mid x mid, mid x hi; hi x lo, hi x mid, hi x hi -- same bits.
+// receives its six products per row in the same order -- lo x hi; mid x mid, mid x hi; hi x lo, hi x mid, hi x hi (B split x dY
+// split) -- same bits.  These are the six products of split_bf16.h (SPLIT_PA / SPLIT_PB), ordered by the B split (one window load
+// each) as the two nested loops below instead of through that table: hi x hi is last in both.
 template <int KS, int WV, int COT>
 __device__ __forceinline__ void ws_wave(const unsigned* __restrict__ s_x, const unsigned* __restrict__ s_dy, f32x4 (&acc)[WsCfg<KS, COT>::TPW],
                                         int lane) {
@@ -218,8 +203,8 @@ __device__ __forceinline__ void ws_block(const WsArgs& a, const int bx, const in
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = __uint_as_float(__float_as_uint(v[e]) & (0u - ((kb >> e) & 1u)));   // zero padding stays an exact zero
             unsigned h0, m0, l0, h1, m1, l1;
-            ws_split_pair(v[0], v[1], h0, m0, l0);
-            ws_split_pair(v[2], v[3], h1, m1, l1);
+            split_pair(v[0], v[1], h0, m0, l0);
+            split_pair(v[2], v[3], h1, m1, l1);
             unsigned* d = ws_smem + sq.lds_word;
             const int split_words = sq.split_words;
             *reinterpret_cast<u32x2*>(d) = u32x2{h0, h1};
@@ -303,11 +288,7 @@ static int launch_ws(const float* x, int x_ctot, int x_coff, int Cin, const floa
     using Cfg = WsCfg<KS, COT>;
     const int tiles_x = (W + 31) / 32, tiles_y = (H + Cfg::TY - 1) / Cfg::TY;
     const int cogs = (Cout + 15) / 16, cigs = (Cin + 15) / 16, zpg = (cogs + COT - 1) / COT;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)conv_wgrad_split_kernel<KS, COT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
+    allow_full_lds<conv_wgrad_split_kernel<KS, COT>>();
     WsArgs a;
     a.x = x; a.in_scale = in_scale; a.in_shift = in_shift; a.dy = dy; a.dw_packed = packed;
     a.x_ctot = x_ctot; a.x_coff = x_coff; a.Cin = Cin; a.in_relu = in_relu; a.dy_ctot = dy_ctot; a.dy_coff = dy_coff; a.Cout = Cout;
@@ -320,11 +301,7 @@ static int launch_ws(const float* x, int x_ctot, int x_coff, int Cin, const floa
 template <int KS, int COT>
 static int launch_ws_table(const WgradDesc* table_dev, int n, int total_blocks, hipStream_t s) {
     using Cfg = WsCfg<KS, COT>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)conv_wgrad_split_table_kernel<KS, COT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
+    allow_full_lds<conv_wgrad_split_table_kernel<KS, COT>>();
     hipLaunchKernelGGL((conv_wgrad_split_table_kernel<KS, COT>), dim3(total_blocks), dim3(Cfg::NW * 64), Cfg::LDS, s, table_dev, n);
     return hipGetLastError() == hipSuccess ? CD_OK : CD_ERR_LAUNCH;
 }

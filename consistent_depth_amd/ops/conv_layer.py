@@ -144,7 +144,7 @@ class _HipConvFn(torch.autograd.Function):
         Cout, cin_g, ks, _ = weight.shape
         G, s = layer.groups, ctx.s
         cout_g = Cout // G
-        lib, stream = _native.lib(), _native.stream_ptr(x.device)
+        lib = _native.lib()
         if ctx.native_s2 and ks == 3:
             return _HipConvFn._backward_strided(ctx, dy)
         if s > 1:   # adjoint of the sub-sampling: zeros between the samples
@@ -152,24 +152,14 @@ class _HipConvFn(torch.autograd.Function):
             dyf[:, :, ::s, ::s] = dy
         else:
             dyf = dy.contiguous()
-        dx = dw = db = None
-        # The weight gradient and the input gradient of a layer are independent: the weight gradient is enqueued on a side stream forked
-        # here and joined before this function returns, so that its workgroups fill the compute units the input gradient's last round of
-        # workgroups leaves idle (288 workgroups of the 24x24 planes on 256 CUs).  Round 6, two alternations on one box: 72.9 / 73.1 ->
-        # 73.6 / 73.7 pairs/s on BASELINE configs[4] (CD_AMD_MIDAS_WGRAD_STREAM=0: one stream).  Same results either way.
-        side = _wgrad_side_stream(x.device) if (ctx.needs_input_grad[0] and ctx.needs_input_grad[1]) else None
-        if side is not None:
-            dw = torch.empty_like(weight)
+
+        def wgrad(dw):
             ws, ws_stride = layer._wgrad_workspace(cout_g, cin_g, ks, x.device)
-            cur = torch.cuda.current_stream(x.device)
-            fork = torch.cuda.Event()
-            fork.record(cur)
-            side.wait_event(fork)
-            with torch.cuda.stream(side):
-                rc = lib.cd_conv2d_wgrad_grouped(_native.dev_ptr(x, "x"), Cin, 0, cin_g, dyf.data_ptr(), Cout, 0, cout_g, G, dw.data_ptr(), 0,
-                                                 ws.data_ptr(), ws_stride, N, H, W, ks, _native.stream_ptr(x.device))
-                _native.check(rc, "cd_conv2d_wgrad_grouped")
-        if ctx.needs_input_grad[0]:
+            rc = lib.cd_conv2d_wgrad_grouped(_native.dev_ptr(x, "x"), Cin, 0, cin_g, dyf.data_ptr(), Cout, 0, cout_g, G, dw.data_ptr(), 0,
+                                             ws.data_ptr(), ws_stride, N, H, W, ks, _native.stream_ptr(x.device))
+            _native.check(rc, "cd_conv2d_wgrad_grouped")
+
+        def dgrad():
             _, pkT = layer._packed(weight, transposed_too=True)
             dx = torch.empty_like(x)
             cfg = _dense_cfg(G, ks, Cout, Cin, N, H, W, x.device)
@@ -177,7 +167,7 @@ class _HipConvFn(torch.autograd.Function):
                 C.conv2d(dyf, pkT[0], Cout, Cin, ks, out=dx, cfg=cfg)
             else:
                 rc = lib.cd_conv2d_fwd_grouped(dyf.data_ptr(), Cout, 0, cout_g, pkT[0].data_ptr(), layer._pack_strideT, None, dx.data_ptr(), Cin, 0,
-                                               cin_g, G, 0, N, H, W, ks, stream)
+                                               cin_g, G, 0, N, H, W, ks, _native.stream_ptr(x.device))
                 _native.check(rc, "cd_conv2d_fwd_grouped (dgrad)")
             if ctx.full_hw is not None:      # (strided 1x1: the input was sub-sampled first)
                 st = layer.stride[0]
@@ -187,60 +177,60 @@ class _HipConvFn(torch.autograd.Function):
                     full = torch.zeros((N, Cin) + ctx.full_hw, dtype=dx.dtype, device=dx.device)
                     full[:, :, ::st, ::st] = dx
                     dx = full
-        if side is not None:
-            done = torch.cuda.Event()
-            done.record(side)
-            torch.cuda.current_stream(x.device).wait_event(done)
-        elif ctx.needs_input_grad[1]:
-            dw = torch.empty_like(weight)
-            ws, ws_stride = layer._wgrad_workspace(cout_g, cin_g, ks, x.device)
-            rc = lib.cd_conv2d_wgrad_grouped(_native.dev_ptr(x, "x"), Cin, 0, cin_g, dyf.data_ptr(), Cout, 0, cout_g, G, dw.data_ptr(), 0,
-                                             ws.data_ptr(), ws_stride, N, H, W, ks, stream)
-            _native.check(rc, "cd_conv2d_wgrad_grouped")
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            from .layers import channel_sum      # (hand-written reduction: cd_channel_sum)
-            dyc = dy.contiguous()
-            db = torch.empty(Cout, dtype=torch.float32, device=dy.device)
-            channel_sum(dyc, 0, Cout, db)
-        return dx, dw, db, None
+            return dx
+
+        return _HipConvFn._run_backward(ctx, dy, wgrad, dgrad)
 
     @staticmethod
     def _backward_strided(ctx, dy):
-        """3x3 / 2 on cd_conv2d_dgrad_strided / cd_conv2d_wgrad_strided: no zero-stuffed dy, the weight gradient on the side stream
-        as in the stride-1 backward."""
+        """3x3 / 2 on cd_conv2d_dgrad_strided / cd_conv2d_wgrad_strided: no zero-stuffed dy."""
         x, weight = ctx.saved_tensors
         layer = ctx.layer
         Cout, cin_g, ks, _ = weight.shape
         G = layer.groups
         cout_g = Cout // G
         dyc = dy.contiguous()
-        dx = dw = db = None
 
-        def wgrad():
-            out = torch.empty_like(weight)
+        def wgrad(dw):
             ws, _ = layer._wgrad_workspace(cout_g, cin_g, ks, x.device)
-            return C.conv2d_wgrad_strided(x, dyc, cin_g, cout_g, ks, out, ws, groups=G)
+            C.conv2d_wgrad_strided(x, dyc, cin_g, cout_g, ks, dw, ws, groups=G)
 
+        def dgrad():
+            layer._packed(weight, transposed_too=True)
+            return C.conv2d_dgrad_strided(dyc, layer._arenaT, cin_g, cout_g, ks, torch.empty_like(x), groups=G)
+
+        return _HipConvFn._run_backward(ctx, dyc, wgrad, dgrad)
+
+    @staticmethod
+    def _run_backward(ctx, dy, wgrad, dgrad):
+        """The skeleton of both backward paths: `wgrad(dw)` fills dw, `dgrad()` returns dx, both enqueue on the current stream."""
+        x, weight = ctx.saved_tensors
+        dx = db = None
+        dw = torch.empty_like(weight) if ctx.needs_input_grad[1] else None
+        # The weight gradient and the input gradient of a layer are independent: the weight gradient is enqueued on a side stream forked
+        # here and joined before this function returns, so that its workgroups fill the compute units the input gradient's last round of
+        # workgroups leaves idle (288 workgroups of the 24x24 planes on 256 CUs).  Round 6, two alternations on one box: 72.9 / 73.1 ->
+        # 73.6 / 73.7 pairs/s on BASELINE configs[4] (CD_AMD_MIDAS_WGRAD_STREAM=0: one stream).  Same results either way.
         side = _wgrad_side_stream(x.device) if (ctx.needs_input_grad[0] and ctx.needs_input_grad[1]) else None
         if side is not None:
             fork = torch.cuda.Event()
             fork.record(torch.cuda.current_stream(x.device))
             side.wait_event(fork)
             with torch.cuda.stream(side):
-                dw = wgrad()
+                wgrad(dw)
         if ctx.needs_input_grad[0]:
-            layer._packed(weight, transposed_too=True)
-            dx = C.conv2d_dgrad_strided(dyc, layer._arenaT, cin_g, cout_g, ks, torch.empty_like(x), groups=G)
+            dx = dgrad()
         if side is not None:
             done = torch.cuda.Event()
             done.record(side)
             torch.cuda.current_stream(x.device).wait_event(done)
         elif ctx.needs_input_grad[1]:
-            dw = wgrad()
+            wgrad(dw)
         if ctx.has_bias and ctx.needs_input_grad[2]:
-            from .layers import channel_sum
-            db = torch.empty(Cout, dtype=torch.float32, device=dy.device)
-            channel_sum(dyc, 0, Cout, db)
+            from .layers import channel_sum      # (hand-written reduction: cd_channel_sum)
+            dyc = dy.contiguous()
+            db = torch.empty(weight.shape[0], dtype=torch.float32, device=dyc.device)
+            channel_sum(dyc, 0, weight.shape[0], db)
         return dx, dw, db, None
 
 
@@ -265,9 +255,7 @@ class HipConv2d(torch.nn.Conv2d):
         n = (lib.cd_conv2d_packed_weight_floats(oc, ic, ks, 0) + 63) // 64 * 64
         arena = torch.zeros(self.groups * n, dtype=torch.float32, device=weight.device)
         views = [arena[g * n:(g + 1) * n] for g in range(self.groups)]
-        dt = np.dtype([("w", "<u8"), ("packed", "<u8"), ("Cout", "<i4"), ("Cin", "<i4"), ("ks", "<i4"), ("tr", "<i4"),
-                       ("OC", "<i4"), ("IC", "<i4"), ("oc_off", "<i4"), ("ic_off", "<i4")])
-        tab = np.zeros(self.groups, dt)
+        tab = np.zeros(self.groups, np.dtype(C.PackTable._DT))
         for g in range(self.groups):
             tab[g] = (weight.data_ptr() + 4 * g * cout_g * cin_g * ks * ks, views[g].data_ptr(), cout_g, cin_g, ks, int(transposed), oc, ic, 0, 0)
         if transposed:

@@ -1,9 +1,9 @@
 #!/bin/bash
 # Static resource census of the hot kernels (no GPU needed): architectural VGPRs, AGPRs, SGPRs, scratch bytes per lane, occupancy.
-#   bash tools/kernel_resources.sh > profiles/kernel_resources_rNN.txt
+#   bash tools/kernel_resources.sh [file ...] > profiles/kernel_resources_rNN.txt      (default: all of the files below)
 REPO=$(cd "$(dirname "$0")/.." && pwd)
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -I $REPO/include -I $REPO/consistent_depth_amd/csrc -c --cuda-device-only -Rpass-analysis=kernel-resource-usage"
-for f in conv_split wgrad_split conv1x1_split wgrad1x1_split loss_sweep; do
+for f in ${@:-conv_split wgrad_split conv1x1_split wgrad1x1_split conv_strided loss_sweep}; do
   extra=""; [ $f = loss_sweep ] && extra="-fno-slp-vectorize"
   echo "== $f"
   /opt/rocm/bin/hipcc $FLAGS $extra -o /tmp/kr_$f.o $REPO/consistent_depth_amd/csrc/$f.hip 2>&1 | python3 -c "
