@@ -56,6 +56,10 @@ SIGNATURES = {
     "cd_conv2d_fwd_strided": (c_i, [c_p, c_i, c_i, c_i, c_p, c_sz, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
     "cd_conv2d_dgrad_strided": (c_i, [c_p, c_i, c_i, c_i, c_p, c_sz, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
     "cd_conv2d_wgrad_strided": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_sz, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "cd_conv2d_stem_supported": (c_i, [c_i, c_i, c_i, c_i, c_i]),
+    "cd_conv2d_stem_fwd": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "cd_conv2d_stem_wgrad": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "cd_conv2d_stem_wgrad_workspace_floats": (c_sz, [c_i, c_i, c_i]),
     "cd_subsample2_fwd": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_p]),
     "cd_subsample2_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
     "cd_set_conv_arith": (c_i, [c_i]),

@@ -2,6 +2,10 @@
 // conv_strided): an fp32 operand is split EXACTLY into three bf16 terms and a product is the six significant cross terms,
 // accumulated in fp32 (the arithmetic is derived in conv_split.hip's header; tests/test_split_arith_cpu.py restates it in numpy).
 // Device-only (inline assembly): not for wgrad_stage_map.h or anything a host compiler sees.
+// HAZARD: the compiler does not see cvt_pk_bf16's inline assembly as a vector instruction and pads no wait states behind it.  A
+// fragment that goes to LDS first is safe; one that feeds an MFMA straight from registers needs two idle states between the last
+// conversion and the matrix instruction (s_nop 1 tied to the fragments, as conv_stem.hip's stem_split8 does) -- without them the MFMA
+// can read the registers' previous content, silently.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -18,7 +18,7 @@ here); the tests pin the layout and compare with an fp64 twin built from the ATe
 
 Everything on the hand-written kernels: every convolution is an ops.conv_layer.HipConv2d (all filters packed by one PackPool launch per
 forward; the three 3x3/2 stage entries and their 1x1/2 shortcuts on the native stride-2 kernels of csrc/conv_strided.hip, the
-3-channel stem on the stride-1-plus-subsampling path), BatchNorm (+ residual) (+ ReLU) and the
+3-channel 7x7/2 stem on the forward / weight-gradient kernels of csrc/conv_stem.hip), BatchNorm (+ residual) (+ ReLU) and the
 max-pool on ops.blocks, and the decoder's reflection padding, nearest x2, skip concat, ELU and sigmoid on ops.resample: each decoder
 convolution is pad_cat (one gather writing the padded input) -> the "same" 3x3 convolution of the padded tensor -> crop_act (its interior
 plus the activation), which is exactly reflection pad + valid Conv2d + activation.  The input's bicubic resize to the feed size (with the

@@ -505,6 +505,51 @@ def conv2d_wgrad_strided(x, dy, cin_g, cout_g, ks, dw, workspace, groups=1, x_co
     return dw
 
 
+# ---------------------------------------------------------------- the 7x7 / 2 RGB stem (cd_conv2d_stem_*)
+def stem_enabled() -> bool:
+    """CD_AMD_CONV_STEM=0: HipConv2d keeps the stride-1-plus-sub-sampling path for the 7x7 / 2 RGB stem (A/B on one box)."""
+    return os.environ.get("CD_AMD_CONV_STEM", "1") != "0"
+
+
+def stem_supported(pass_, ks, stride, cin, cout) -> bool:
+    """cd_conv2d_stem_supported under the current arithmetic mode (mode 0 has no stem kernels).
+    pass_: 0 forward, 2 weight gradient (1, the input gradient, is never supported)."""
+    lib = _native.lib()
+    return bool(lib.cd_conv2d_stem_supported(pass_, ks, stride, cin, cout)) and lib.cd_get_conv_arith() >= 1
+
+
+def stem_wgrad_workspace_floats(cout, cin, ks=7) -> int:
+    return _native.lib().cd_conv2d_stem_wgrad_workspace_floats(cout, cin, ks)
+
+
+def conv2d_stem(x, w, bias=None, out=None, x_coff=0, y_coff=0, stride=2):
+    """out[:, y_coff : y_coff + Cout] = conv(x[:, x_coff : x_coff + Cin], w, stride 2, padding 3) + bias for the PLAIN filter
+    w (Cout, Cin <= 4, 7, 7): no packed filter.  x is (N, *, H, W), out (N, *, ceil(H/2), ceil(W/2))."""
+    N, x_ctot, H, W = x.shape
+    Cout, Cin, ks, _ = w.shape
+    if out is None:
+        out = torch.empty(N, Cout, (H + 1) // 2, (W + 1) // 2, dtype=torch.float32, device=x.device)
+    rc = _native.lib().cd_conv2d_stem_fwd(
+        _native.dev_ptr(x, "x"), x_ctot, x_coff, Cin, _native.dev_ptr(w, "w"), _native.dev_ptr(bias, "bias") if bias is not None else None,
+        _native.dev_ptr(out, "out"), out.shape[1], y_coff, Cout, N, H, W, ks, stride, _native.stream_ptr(x.device))
+    _native.check(rc, "cd_conv2d_stem_fwd")
+    return out
+
+
+def conv2d_stem_wgrad(x, dy, dw, workspace, accumulate=False, x_coff=0, dy_coff=0, stride=2):
+    """dw (Cout, Cin <= 4, 7, 7) (+)= the weight gradient of conv2d_stem from x (N, *, H, W) and dy (N, *, ceil(H/2), ceil(W/2)).
+    workspace: at least stem_wgrad_workspace_floats(Cout, Cin) floats."""
+    N, x_ctot, H, W = x.shape
+    Cout, Cin, ks, _ = dw.shape
+    if workspace.numel() < stem_wgrad_workspace_floats(Cout, Cin, ks):
+        raise RuntimeError("conv2d_stem_wgrad: workspace smaller than cd_conv2d_stem_wgrad_workspace_floats")
+    rc = _native.lib().cd_conv2d_stem_wgrad(
+        _native.dev_ptr(x, "x"), x_ctot, x_coff, Cin, _native.dev_ptr(dy, "dy"), dy.shape[1], dy_coff, Cout, _native.dev_ptr(dw, "dw"),
+        _native.dev_ptr(workspace, "workspace"), int(accumulate), N, H, W, ks, stride, _native.stream_ptr(x.device))
+    _native.check(rc, "cd_conv2d_stem_wgrad")
+    return dw
+
+
 def subsample2(x, C=None, coff=0, out=None):
     """out (N, C, ceil(H/2), ceil(W/2)) = x[:, coff : coff + C, ::2, ::2]."""
     N, ctot, H, W = x.shape

@@ -11,9 +11,13 @@ Same parameters and state_dict keys as nn.Conv2d (a checkpoint loads unchanged).
     16-wide MFMA column tile is half empty;
   * stride 2: native kernels (csrc/conv_strided.hip) wherever cd_conv2d_strided_supported says yes -- 3x3 with >= 8 input channels per
     group, dense and grouped, on cd_conv2d_fwd_strided / _dgrad_strided / _wgrad_strided (no full-resolution output, no zero-stuffed
-    gradient); 1x1 on cd_subsample2_fwd / _bwd around the stride-1 1x1 kernels.  Elsewhere (the RGB stems, arithmetic mode 0, or
-    CD_AMD_CONV_STRIDED=0 for A/B runs) the stride-1 "same" output sampled at even positions: identical values, 4x the MACs of a
-    strided kernel and framework copy / fill kernels around it.
+    gradient); 1x1 on cd_subsample2_fwd / _bwd around the stride-1 1x1 kernels; the 7x7 / 2 RGB stem (<= 4 input channels, dense) on
+    cd_conv2d_stem_fwd / cd_conv2d_stem_wgrad (csrc/conv_stem.hip), which read the PLAIN filter -- such a layer has no packed filter
+    and a PackPool skips it.  The stem kernels have NO input gradient (an image needs none, and 3 output channels would waste the
+    matrix tile): if x.requires_grad, dx alone keeps the zero-stuffed dy + stride-1 path (and the layer its transposed pack), y and
+    dw stay native and the other layers of a PackPool are not touched.  Elsewhere (arithmetic mode 0, CD_AMD_CONV_STRIDED=0 or, for the stem alone, CD_AMD_CONV_STEM=0 for A/B runs)
+    the stride-1 "same" output sampled at even positions: identical values, 4x the MACs of a strided kernel and framework copy /
+    fill kernels around it.
   * 1x1, dense (the bottleneck entry / exit convolutions: 2/3 of ResNeXt-101's multiply-adds, at 12x12 .. 96x96 images with
     256 .. 2048 channels): a plain GEMM  Y[n] = W [Cout x Cin] . X[n] [Cin x HW]  -- not a stencil.  On the hand-written kernels like
     everything else (no library GEMM on the path; rounds 3-5 carried a torch.matmul / bmm route behind CD_AMD_MIDAS_1X1=gemm, removed in
@@ -47,6 +51,9 @@ class PackPool:
 
     def run(self):
         layers = [l for l in self.layers if l._uses_packed()]
+        if not layers:      # (a pool of stem layers only: nothing to pack)
+            self._key, self.fresh = (), True
+            return
         key = tuple(l.weight.data_ptr() for l in layers)
         if key != self._key:      # first use, or the optimiser re-homed the parameters: rebuild the descriptors
             tabs = []
@@ -104,13 +111,23 @@ class _HipConvFn(torch.autograd.Function):
         G, s = layer.groups, layer.stride[0]
         cout_g = Cout // G
         ctx.full_hw = None
-        # stride 2 on the native kernels wherever the library has them (CD_AMD_CONV_STRIDED=0, arithmetic mode 0, the RGB stems: the
+        # stride 2 on the native kernels wherever the library has them (CD_AMD_CONV_STRIDED=0, arithmetic mode 0: the
         # stride-1-plus-sub-sampling path below)
         ctx.native_s2 = s == 2 and C.strided_enabled() and all(C.strided_supported(p, ks, 2, cin_g, cout_g) for p in (0, 1, 2))
         if ctx.native_s2 and ks == 3:
             x = x.contiguous()
             layer._packed(weight)
             y = C.conv2d_strided(x, layer._arena, cin_g, cout_g, ks, groups=G, bias=bias)
+            ctx.layer, ctx.hw, ctx.s = layer, tuple(x.shape[2:]), s
+            ctx.save_for_backward(x, weight)
+            ctx.has_bias = bias is not None
+            return y
+        ctx.stem = layer._stem_now()
+        if ctx.stem:               # the 7x7 / 2 RGB stem: y at output resolution from the plain filter
+            if not (weight.is_cuda and weight.is_contiguous() and weight.dtype == torch.float32):
+                raise RuntimeError("HipConv2d: weights must be contiguous fp32 on the HIP device (no CPU path)")
+            x = x.contiguous()
+            y = C.conv2d_stem(x, weight, bias)
             ctx.layer, ctx.hw, ctx.s = layer, tuple(x.shape[2:]), s
             ctx.save_for_backward(x, weight)
             ctx.has_bias = bias is not None
@@ -147,20 +164,27 @@ class _HipConvFn(torch.autograd.Function):
         lib = _native.lib()
         if ctx.native_s2 and ks == 3:
             return _HipConvFn._backward_strided(ctx, dy)
-        if s > 1:   # adjoint of the sub-sampling: zeros between the samples
+        dyc = dy.contiguous() if ctx.stem else None
+        if ctx.stem and not ctx.needs_input_grad[0]:
+            dyf = None      # the stem's weight gradient reads dy at its own resolution: no full-resolution tensor
+        elif s > 1:   # adjoint of the sub-sampling: zeros between the samples
             dyf = torch.zeros(N, Cout, H, W, dtype=torch.float32, device=dy.device)
             dyf[:, :, ::s, ::s] = dy
         else:
             dyf = dy.contiguous()
 
         def wgrad(dw):
+            if ctx.stem:
+                C.conv2d_stem_wgrad(x, dyc, dw, layer._stem_workspace(Cout, cin_g, ks, x.device))
+                return
             ws, ws_stride = layer._wgrad_workspace(cout_g, cin_g, ks, x.device)
             rc = lib.cd_conv2d_wgrad_grouped(_native.dev_ptr(x, "x"), Cin, 0, cin_g, dyf.data_ptr(), Cout, 0, cout_g, G, dw.data_ptr(), 0,
                                              ws.data_ptr(), ws_stride, N, H, W, ks, _native.stream_ptr(x.device))
             _native.check(rc, "cd_conv2d_wgrad_grouped")
 
         def dgrad():
-            _, pkT = layer._packed(weight, transposed_too=True)
+            # (the stem's dx: a transposed pack of the layer's own -- a stem layer is no member of a PackPool)
+            pkT = layer._stem_packT(weight) if ctx.stem else layer._packed(weight, transposed_too=True)[1]
             dx = torch.empty_like(x)
             cfg = _dense_cfg(G, ks, Cout, Cin, N, H, W, x.device)
             if cfg is not None:
@@ -241,10 +265,34 @@ class HipConv2d(torch.nn.Conv2d):
         if not (k[0] == k[1] and k[0] in C.KERNEL_SIZES and s[0] == s[1] and s[0] in (1, 2) and p[0] == p[1] == (k[0] - 1) // 2
                 and self.dilation == (1, 1) and self.padding_mode == "zeros"):
             raise ValueError(f"HipConv2d: unsupported geometry kernel {k} stride {s} padding {p}")
-        self._pk = self._pkT = self._table = self._tableT = self._wptr = self._ws = self._pool = None
+        self._pk = self._pkT = self._table = self._tableT = self._wptr = self._ws = self._pool = self._stem_ws = None
+        self._stem_pkT = self._stem_tableT = self._stem_wptr = None
+
+    def _stem_now(self):
+        """This call runs on the stem kernels (forward and weight gradient): the geometry, the switches and the arithmetic mode agree."""
+        k, cin, cout = self.kernel_size[0], self.in_channels, self.out_channels
+        return (self.stride[0] == 2 and self.groups == 1 and C.strided_enabled() and C.stem_enabled()
+                and all(C.stem_supported(p, k, 2, cin, cout) for p in (0, 2)))
 
     def _uses_packed(self):
-        return True
+        """False for a layer on the stem kernels: they read the plain filter.  (Evaluated per call, not once: the arithmetic mode and
+        the A/B switches may change between calls, and the stride-1 path they select needs the packs.)"""
+        return not self._stem_now()
+
+    def _stem_packT(self, weight):
+        """The transposed pack behind the dx of a stem layer whose input asked for a gradient, packed here and now.  It is the layer's
+        own, never a PackPool's: asking for dx changes nothing for the other layers of a network."""
+        if self._stem_pkT is None or self._stem_wptr != weight.data_ptr():
+            self._stem_pkT, self._stem_tableT, _ = self._build(weight, True)
+            self._stem_wptr = weight.data_ptr()
+        _native.check(_native.lib().cd_conv2d_pack_weights_table(self._stem_tableT.data_ptr(), self.groups, _native.stream_ptr(weight.device)),
+                      "cd_conv2d_pack_weights_table")
+        return self._stem_pkT
+
+    def _stem_workspace(self, cout, cin, ks, device):
+        if self._stem_ws is None:
+            self._stem_ws = torch.empty(C.stem_wgrad_workspace_floats(cout, cin, ks), dtype=torch.float32, device=device)
+        return self._stem_ws
 
     def _build(self, weight, transposed):
         """Packed buffers of every group (zeroed once: padding elements are never written) + the pack table."""

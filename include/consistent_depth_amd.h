@@ -330,6 +330,22 @@ int cd_conv2d_dgrad_strided(const float* dy, int dy_ctot, int dy_coff, int cout_
 int cd_conv2d_wgrad_strided(const float* x, int x_ctot, int x_coff, int cin_g, const float* dy, int dy_ctot, int dy_coff, int cout_g, int groups,
                             float* dw, int accumulate, float* workspace, size_t workspace_group_stride, int N, int H, int W, int ks, int stride,
                             void* stream);
+/* The 7x7 / 2 RGB stem, nn.Conv2d(cin <= 4, cout, 7, stride = 2, padding = 3), groups = 1: forward and weight gradient on kernels of
+ * their own (conv_stem.hip; H, W, Ho, Wo as above).  The reduction runs over the flattened taps (ci, ky, kx) -- 147 at cin = 3, padded
+ * to the matrix step -- so the filter `w` is the PLAIN [cout][cin][7][7] tensor: no packed filter.  Split-bf16 arithmetic (modes 1
+ * and 2), fp32-accurate, no atomics, bit-reproducible.  There is no input gradient (images need none).
+ *   cd_conv2d_stem_supported (host only): 1 for pass 0 (forward) and 2 (weight gradient) of ks = 7, stride = 2, 1 <= cin <= 4,
+ *     cout >= 8; 0 for pass 1 and everything else.  (cd_conv2d_strided_supported keeps answering 0 for this geometry.)
+ *   cd_conv2d_stem_fwd: y = conv(x) + bias (bias may be NULL); every element of the y slice is written.
+ *   cd_conv2d_stem_wgrad: dw [cout][cin][7][7] (+)= the weight gradient, dy at its own resolution (no zero-stuffed plane).  workspace:
+ *     cd_conv2d_stem_wgrad_workspace_floats(cout, cin, ks) floats of per-workgroup partial sums, added in a fixed order.
+ * CD_ERR_UNSUPPORTED, nothing launched: any other geometry, arithmetic mode 0.  No host synchronisation, no allocation: capturable. */
+int cd_conv2d_stem_supported(int pass, int ks, int stride, int cin, int cout);
+int cd_conv2d_stem_fwd(const float* x, int x_ctot, int x_coff, int cin, const float* w, const float* bias, float* y, int y_ctot, int y_coff,
+                       int cout, int N, int H, int W, int ks, int stride, void* stream);
+int cd_conv2d_stem_wgrad(const float* x, int x_ctot, int x_coff, int cin, const float* dy, int dy_ctot, int dy_coff, int cout, float* dw,
+                         float* workspace, int accumulate, int N, int H, int W, int ks, int stride, void* stream);
+size_t cd_conv2d_stem_wgrad_workspace_floats(int cout, int cin, int ks);
 /* y[N][C][Ho][Wo] = x[:, coff : coff+C, ::2, ::2] of x[N][ctot][H][W], and its adjoint: dx[:, coff : coff+C] = dy at even (row, column),
  * 0 elsewhere -- the whole [H][W] plane is written in one pass.  The two halves of a 1x1 / 2 convolution around the stride-1 1x1 entries. */
 int cd_subsample2_fwd(const float* x, int ctot, int coff, int C, float* y, int N, int H, int W, void* stream);

@@ -4,7 +4,8 @@
     python tools/conv_strided_bench.py [--iters 20] [--warmup 3]
 
 Shapes: the three stage entries of ResNet-18 at the KITTI feed, the three strided grouped 3x3 of ResNeXt-101 32x8d at 384x384 and
-the 1x1 / 2 down-sample shortcuts, N = 8.  Per pass (forward, input gradient, weight gradient): median of `iters` launches timed
+the 1x1 / 2 down-sample shortcuts, N = 8; then the two 7x7 / 2 RGB stems (csrc/conv_stem.hip: monodepth2 at N = 8, 320 x 1024 and midas2
+at N = 16, 384 x 384; forward and weight gradient only, native against CD_AMD_CONV_STEM=0).  Per pass (forward, input gradient, weight gradient): median of `iters` launches timed
 with HIP events, the speed-up, and the fraction of the split-bf16 roof (2500 / 6 TFLOP/s, bench.py's roofline_conv) on the
 STRIDED multiply-add count.  The passes are isolated through autograd: forward = the layer call, input gradient = grad w.r.t. x
 only, weight gradient = grad w.r.t. the weight only."""
@@ -24,6 +25,9 @@ SHAPES = [  # (name, Cin, Cout, k, groups, H, W)
     ("resnet18 layer4.0 1x1", 256, 512, 1, 1, 20, 64),
     ("resnext101 layer2.0 1x1", 256, 512, 1, 1, 96, 96), ("resnext101 layer3.0 1x1", 512, 1024, 1, 1, 48, 48),
     ("resnext101 layer4.0 1x1", 1024, 2048, 1, 1, 24, 24),
+]
+STEMS = [  # (name, Cin, Cout, k, groups, H, W, N): no input gradient (an image needs none)
+    ("monodepth2 stem 7x7", 3, 64, 7, 1, 320, 1024, 8), ("midas2 stem 7x7", 3, 64, 7, 1, 384, 384, 16),
 ]
 ROOF = 2500e12 / 6
 N = 8
@@ -51,26 +55,29 @@ def main():
         return statistics.median(ts)
 
     print(f"{'shape':32s} {'pass':6s} {'native us':>10s} {'emulated us':>12s} {'speed-up':>9s} {'roof %':>7s}")
-    for name, Cin, Cout, k, G, H, W in SHAPES:
+    rows = [(s, N, "CD_AMD_CONV_STRIDED", ("fwd", "dgrad", "wgrad")) for s in SHAPES] + [(s[:7], s[7], "CD_AMD_CONV_STEM", ("fwd", "wgrad")) for s in STEMS]
+    for (name, Cin, Cout, k, G, H, W), n_img, switch, passes in rows:
         torch.manual_seed(0)
         layer = HipConv2d(Cin, Cout, k, 2, (k - 1) // 2, groups=G, bias=False).cuda()
-        x = torch.randn(N, Cin, H, W, device="cuda")
+        x = torch.randn(n_img, Cin, H, W, device="cuda")
         xg = x.clone().requires_grad_(True)
-        dy = torch.randn(N, Cout, (H + 1) // 2, (W + 1) // 2, device="cuda")
-        macs = N * dy.shape[2] * dy.shape[3] * Cout * (Cin // G) * k * k
+        dy = torch.randn(n_img, Cout, (H + 1) // 2, (W + 1) // 2, device="cuda")
+        macs = n_img * dy.shape[2] * dy.shape[3] * Cout * (Cin // G) * k * k
         res = {}
         for mode in ("1", "0"):
-            os.environ["CD_AMD_CONV_STRIDED"] = mode
-            layer.weight.requires_grad_(False)
-            y_dx = layer(xg)
+            os.environ[switch] = mode
+            if "dgrad" in passes:
+                layer.weight.requires_grad_(False)
+                y_dx = layer(xg)
             layer.weight.requires_grad_(True)
             y_dw = layer(x)
             with torch.no_grad():
                 res[mode, "fwd"] = timed(lambda: layer(x))
-            res[mode, "dgrad"] = timed(lambda: torch.autograd.grad(y_dx, xg, dy, retain_graph=True))
+            if "dgrad" in passes:
+                res[mode, "dgrad"] = timed(lambda: torch.autograd.grad(y_dx, xg, dy, retain_graph=True))
             res[mode, "wgrad"] = timed(lambda: torch.autograd.grad(y_dw, layer.weight, dy, retain_graph=True))
-        os.environ["CD_AMD_CONV_STRIDED"] = "1"
-        for p in ("fwd", "dgrad", "wgrad"):
+        os.environ[switch] = "1"
+        for p in passes:
             nat, emu = res["1", p], res["0", p]
             print(f"{name:32s} {p:6s} {nat:10.1f} {emu:12.1f} {emu / nat:8.2f}x {100 * 2 * macs / ROOF / (nat * 1e-6):7.1f}")
 
