@@ -43,6 +43,9 @@ SIGNATURES = {
     "cd_warp_image": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),
     "cd_depth_to_points": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
     "cd_frame_median_scales": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
+    "cd_depth_range": (c_i, [c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_p, c_p, c_p]),
+    "cd_depth_range_fold": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p, c_p]),
+    "cd_depth_colorize": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_p]),
     "cd_conv2d_packed_weight_floats": (c_sz, [c_i, c_i, c_i, c_i]),
     "cd_conv2d_pack_weights": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p]),
     "cd_conv2d_pack_weights_table": (c_i, [c_p, c_i, c_p]),

@@ -11,18 +11,11 @@
 // two middle values.  A NaN among the selected ratios (0 / 0: a finite COLMAP value of 0 under a 0 initial value) makes the median
 // NaN, like numpy's.  HBM-bound in principle (8 B per pixel, re-read 5-6 times from L2: a frame is 0.7 MB); an offline stage.
 #include "cd_common.h"
+#include "order_key.h"
 
 namespace cd {
 
 constexpr int kScaleThreads = 1024;
-
-__device__ __forceinline__ unsigned order_key(float x) {        // monotonic: a < b  <=>  key(a) < key(b)  (-0 < +0: both are the value 0)
-    const unsigned b = __float_as_uint(x);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float key_value(unsigned k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
 
 __global__ __launch_bounds__(kScaleThreads) void frame_median_scale_kernel(const float* __restrict__ inv_src, const float* __restrict__ inv_cmp,
                                                                            int HW, float* __restrict__ scale_out, int* __restrict__ n_out,

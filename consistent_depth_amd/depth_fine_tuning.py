@@ -8,7 +8,9 @@ with `.out_dir`, `.save_depth(dir, frames)` (:164-199), `.fine_tune(writer=None)
     <out_dir>/checkpoints/%04d.pth                      netG.state_dict()
     <out_dir>/eval/depth_%06d_e%04d_iter%06d.raw        inverse depth, first sighting of a frame
     <out_dir>/eval/loss_e%04d_iter%06d.json             {loss_name: {"[i, j]": v}, "mean": {...}}
+    <out_dir>/eval/depth_%06d_e%04d_iter%06d.png        its colour-mapped preview, range [0, vis_depth_scale]
     <dir>/depth/frame_%06d.raw                          inverse depth (save_depth)
+    <dir>/depth/frame_%06d.png                          its preview, one range for the whole directory
 
 What differs, by design (MI355X-first):
   * the whole frame-pair dataset lives in HBM (loaders/pair_store.py) -- no DataLoader workers;
@@ -20,8 +22,8 @@ What differs, by design (MI355X-first):
     losses are fetched only every `print_freq` steps and at validation;
   * shuffling uses a seeded numpy permutation (the reference is unseeded); `--seed` is an
     extension flag.
-PNG visualisations and tensorboard images are cosmetic and out of scope (SURVEY.md section 2
-row 12); scalars are written if a `writer` with add_scalar() is passed.
+The PNG previews come from utils/visualization.py (csrc/visualize.hip; CD_AMD_PREVIEWS=0 skips them); tensorboard
+images are out of scope; scalars are written if a `writer` with add_scalar() is passed.
 """
 from __future__ import annotations
 
@@ -40,7 +42,7 @@ from .loaders.pair_store import PairStore
 from .loaders.video_dataset import VideoFrameDataset
 from .loss.loss_params import LossParams
 from .monodepth.depth_model_registry import get_depth_model
-from .utils import image_io
+from .utils import image_io, visualization
 
 
 class DepthFineTuningParams:
@@ -95,12 +97,15 @@ class DepthFineTuner:
         self.store = store
         self.seed = getattr(params, "seed", 0)
         self._resume = None
+        self.vis_depth_scale = None          # 1-element device tensor: the upper end of the validation previews' range
 
-    def resume_from(self, state_dict, exp_avg, exp_avg_sq, adam_steps: int, epoch: int, total_iters: int):
+    def resume_from(self, state_dict, exp_avg, exp_avg_sq, adam_steps: int, epoch: int, total_iters: int, vis_depth_scale=None):
         """EXTENSION (the reference cannot resume): the next fine_tune() continues a run at the START of `epoch` -- network weights
         and BatchNorm buffers from `state_dict` (a checkpoints/%04d.pth), the Adam moments as {parameter name: tensor} dicts, the
         number of optimiser steps taken and the `total_iters` (pairs) counter that names the validation files.  The validation
-        sweep before the first epoch is not repeated (it belongs to the end of epoch `epoch - 1`)."""
+        sweep before the first epoch is not repeated (it belongs to the end of epoch `epoch - 1`).  `vis_depth_scale`: the range of the
+        validation previews of the run that is continued (its first batch's maximum inverse depth); None = the first sweep after the
+        resume sets it."""
         from .monodepth.hourglass import load_state_dict_any_prefix
         net = self.model.netG if hasattr(self.model, "netG") else self.model.model
         load_state_dict_any_prefix(net, state_dict)
@@ -125,7 +130,8 @@ class DepthFineTuner:
                 raise ValueError(f"resume_from: epoch {epoch} of {n_pairs} pairs (batch {self.params.batch_size}) allows at most "
                                  f"total_iters {int(epoch) * n_pairs} and adam_steps {int(epoch) * per_epoch}, got {total_iters} / {adam_steps}")
         self._resume = dict(m1=[exp_avg[n] for n in names], m2=[exp_avg_sq[n] for n in names], steps=int(adam_steps),
-                            epoch=int(epoch), total_iters=int(total_iters))
+                            epoch=int(epoch), total_iters=int(total_iters),
+                            vis_depth_scale=None if vis_depth_scale is None else float(vis_depth_scale))
 
     # ------------------------------------------------------------------ depth export (:164-199)
     @torch.no_grad()
@@ -144,6 +150,8 @@ class DepthFineTuner:
             get = lambda f: ds[lookup[f]][0][None]  # noqa: E731
         # batched eval-mode forward; inverse depth stays on the device, file writes run on a background thread
         bs = max(1, 2 * self.params.batch_size)
+        previews = visualization.previews_enabled()
+        resident = {}            # file name -> exported plane, kept on the device for the preview pass
         with image_io.AsyncRawWriter(device=self.store.device if self.store is not None else None) as writer:
             for s0 in range(0, len(frames), bs):
                 chunk = frames[s0:s0 + bs]
@@ -151,6 +159,10 @@ class DepthFineTuner:
                 inv = self.model.forward(images).detach().float().reciprocal()
                 for i, f in enumerate(chunk):
                     writer.submit(pjoin(depth_dir, f"frame_{f:06d}.raw"), inv[i].reshape(inv.shape[-2:]))
+                    if previews:
+                        resident[f"frame_{f:06d}.raw"] = inv[i].reshape(inv.shape[-2:])
+        if previews:             # one range over the whole directory (files of earlier runs included), like force=True in the reference (:198-199)
+            visualization.visualize_depth_dir(depth_dir, depth_dir, force=True, resident=resident)
 
     # ------------------------------------------------------------------ training (:201-310)
     def fine_tune(self, writer=None):
@@ -178,6 +190,7 @@ class DepthFineTuner:
                 print(f"Done Validation for epoch {epoch} ({niters} iterations)")
 
         first_epoch, total_iters = 0, 0
+        self.vis_depth_scale = None          # (:256) fixed again by the first batch of this call's first sweep
         if self._resume is not None:
             r, self._resume = self._resume, None
             base = getattr(step, "step", step)
@@ -185,6 +198,8 @@ class DepthFineTuner:
             order = [by_id[id(q)] for q in base.opt._params]      # FlatAdam's parameter order (= model.parameters() order)
             base.opt.load_moments([r["m1"][i] for i in order], [r["m2"][i] for i in order], r["steps"])
             first_epoch, total_iters = r["epoch"], r["total_iters"]
+            if r["vis_depth_scale"] is not None:
+                self.vis_depth_scale = torch.full((1,), r["vis_depth_scale"], dtype=torch.float32, device=store.device)
         else:
             validate(0, 0)
         for epoch in range(first_epoch, p.num_epochs):
@@ -276,18 +291,34 @@ class DepthFineTuner:
         evaluator = getattr(base, "_evaluator", None)
         if evaluator is None:
             evaluator = base._evaluator = GraphedEvaluate(base)
-        with image_io.AsyncRawWriter(device=store.device) as writer:     # the files of this sweep are on disk when the block ends
+        previews = visualization.previews_enabled()
+        zero = torch.zeros(1, dtype=torch.float32, device=store.device) if previews else None    # depth_min of the sweep's previews (:352)
+        if previews and self.vis_depth_scale is None and self.world > 1 and self.rank != 0:
+            # the scale is the maximum of the sweep's FIRST batch (:352-354), which rank 0 evaluates: received before anything is rendered
+            scale = torch.empty(1, dtype=torch.float32, device=store.device)
+            parallel.broadcast_([scale], src=0)
+            self.vis_depth_scale = scale
+        with image_io.AsyncRawWriter(device=store.device, threads=image_io.PNG_ENCODER_THREADS if previews else 1) as writer:
+            # (the files of this sweep are on disk when the block ends)
             for (chunk, ids), ids_dev in zip(chunks, plan_dev):
                 raw, parts, metadata = evaluator(store, ids_dev)
                 idx = metadata["geometry_consistency"]["indices"]
                 rows.append(torch.cat([idx.float()] + [parts[n].reshape(-1, 1).float() for n in names], 1))
                 inv = self._depth_from_raw(raw).reciprocal()
+                if previews:
+                    if self.vis_depth_scale is None:      # rank 0, batch 0: np.max of the whole batch (NaN propagates), kept on the device
+                        self.vis_depth_scale = visualization.nan_max(inv)
+                        if self.world > 1:
+                            parallel.broadcast_([self.vis_depth_scale], src=0)
+                    rgb = visualization.colorize(inv, zero, self.vis_depth_scale)
                 done = set()
                 for b, pid in enumerate(ids):
                     for k, f in enumerate(frames_of[pid]):
                         if first[f] == chunk and f not in done:   # the reference keeps the first sighting (:343-360)
                             done.add(f)
                             writer.submit(pjoin(self.out_dir, "eval", f"depth_{f:06d}{suf}.raw"), inv[b, k])
+                            if previews:
+                                writer.submit_png(pjoin(self.out_dir, "eval", f"depth_{f:06d}{suf}.png"), rgb[b, k])
         table = torch.cat(rows, 0) if rows else torch.zeros(0, 2 + len(names), device=store.device)
         if self.world > 1:
             import torch.distributed as dist

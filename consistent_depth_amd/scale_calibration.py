@@ -6,7 +6,8 @@ Mirrors /root/reference/scale_calibration.py:228-319 (`calibrate_scale`, from "C
 skip rules (a frame without a converted COLMAP map is skipped; a frame whose finite COLMAP pixels are fewer than
 --dense_pixel_ratio of the image is invalid), same numbers: the medians come from ONE launch of `cd_frame_median_scales`
 (csrc/scale.hip: exact selection, bit for bit np.median), the rest is host bookkeeping on a handful of floats.
-What is NOT here: running COLMAP and converting its depth maps (:84-226, out of scope: SURVEY.md section 2), the PNG visualisations.
+The scaled maps get their colour-mapped PNG previews (:287-290; utils/visualization.py, CD_AMD_PREVIEWS=0 skips them).
+What is NOT here: running COLMAP and converting its depth maps (:84-226, out of scope: SURVEY.md section 2).
 `ScaleCalibrationParams` carries the reference's two flags (:25-34).
 """
 from __future__ import annotations
@@ -18,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _native
-from .utils import image_io
+from .utils import image_io, visualization
 
 
 class ScaleCalibrationParams:
@@ -66,14 +67,16 @@ def compute_frame_scales(frames, src_depth_fmt: str, converted_depth_fmt: str, s
     os.makedirs(os.path.dirname(scaled_depth_fmt), exist_ok=True)
     present = [i for i in frames if os.path.isfile(converted_depth_fmt.format(i))]       # (:257-261: missing maps are skipped)
     scales_map = {}
+    previews = visualization.previews_enabled()
+    resident = {}       # file name -> scaled plane, kept on the device for the preview pass
     for s0 in range(0, len(present), chunk):
         ids = present[s0:s0 + chunk]
         src = [image_io.load_raw_float32_image(src_depth_fmt.format(i)) for i in ids]
         cmp_ = [nearest_resize(image_io.load_raw_float32_image(converted_depth_fmt.format(i)), src[k].shape[:2]) for k, i in enumerate(ids)]
         inv_src = torch.as_tensor(np.stack(src)).to(device)
         inv_cmp = torch.as_tensor(np.stack(cmp_)).to(device)
-        scales, n_valid, scaled = frame_median_scales(inv_src, inv_cmp)
-        scales, n_valid, scaled = scales.cpu().numpy(), n_valid.cpu().numpy(), scaled.cpu().numpy()
+        scales, n_valid, scaled_dev = frame_median_scales(inv_src, inv_cmp)
+        scales, n_valid, scaled = scales.cpu().numpy(), n_valid.cpu().numpy(), scaled_dev.cpu().numpy()
         size = inv_src.shape[1] * inv_src.shape[2]
         for k, i in enumerate(ids):
             if n_valid[k] / size < dense_pixel_ratio:        # not enough valid pixels: the frame is invalid (:270-272)
@@ -81,6 +84,11 @@ def compute_frame_scales(frames, src_depth_fmt: str, converted_depth_fmt: str, s
             print(f"Scale[{i}]: median={scales[k]}")
             scales_map[i] = float(scales[k])
             image_io.save_raw_float32_image(scaled_depth_fmt.format(i), scaled[k])
+            if previews:
+                resident[os.path.basename(scaled_depth_fmt.format(i))] = scaled_dev[k]
+    if previews:        # (:287-290) one range over the directory, minimum to maximum; the planes of this call are not read back from disk
+        scaled_dir = os.path.dirname(scaled_depth_fmt)
+        visualization.visualize_depth_dir(scaled_dir, scaled_dir, force=True, resident=resident, device=device)
     return scales_map
 
 

@@ -60,13 +60,23 @@ def save_mask_png(file_name: str, mask: np.ndarray) -> None:
     Image.fromarray((np.asarray(mask) > 0).astype(np.uint8) * 255).save(file_name)
 
 
-class AsyncRawWriter:
-    """Writes device tensors as `.raw` float32 images OFF the critical path: `submit` enqueues a device-to-pinned-host copy on
-    a side stream (ordered after the producing stream by an event) and returns at once; a background thread waits for each
-    copy and writes the file.  `close()` (or leaving the `with` block) drains the queue and re-raises a writer error.
-    Replaces the reference's blocking per-frame `.cpu().numpy()` + write (depth_fine_tuning.py:185-199)."""
+PNG_ENCODER_THREADS = 4     # PIL releases the GIL inside zlib: up to this many PNG encodes run side by side
 
-    def __init__(self, device=None, max_pending: int = 64):
+
+def save_png(file_name: str, image: np.ndarray) -> None:
+    """8-bit (H,W) grey or (H,W,3) R,G,B image."""
+    from PIL import Image
+    Image.fromarray(np.ascontiguousarray(image, dtype=np.uint8)).save(file_name, format="PNG")
+
+
+class AsyncRawWriter:
+    """Writes device tensors as `.raw` float32 images (`submit`) or 8-bit PNGs (`submit_png`) OFF the critical path: a submit
+    enqueues a device-to-pinned-host copy on a side stream (ordered after the producing stream by an event) and returns at once;
+    `threads` background threads wait for each copy and encode / write the file.  `close()` (or leaving the `with` block) drains
+    the queue and re-raises a writer error.  Replaces the reference's blocking per-frame `.cpu().numpy()` + write
+    (depth_fine_tuning.py:185-199, :351-371)."""
+
+    def __init__(self, device=None, max_pending: int = 64, threads: int = 1):
         import queue
         import threading
         import torch
@@ -74,24 +84,37 @@ class AsyncRawWriter:
         self._stream = torch.cuda.Stream(device=device)
         self._q = queue.Queue(maxsize=max_pending)
         self._err = None
-        self._thread = threading.Thread(target=self._run, name="cd-raw-writer", daemon=True)
-        self._thread.start()
+        # threads = 1 (the default, and every sweep with the previews off) is the single writer this class always had: files are
+        # written one by one in submission order.  With more threads the files of a sweep -- `.raw` ones included -- finish in no
+        # fixed order; each file's bytes do not depend on it, and all of them are on disk when close() returns.
+        self._threads = [threading.Thread(target=self._run, name=f"cd-raw-writer-{i}", daemon=True) for i in range(max(1, int(threads)))]
+        for th in self._threads:
+            th.start()
 
     def submit(self, file_name: str, image) -> None:
+        self._submit(file_name, image, self._torch.float32, save_raw_float32_image)
+
+    def submit_png(self, file_name: str, image) -> None:
+        """image: (H,W) or (H,W,3) uint8 device tensor, R,G,B."""
+        if image.dtype != self._torch.uint8:
+            raise TypeError(f"submit_png: expected a uint8 image, got {image.dtype}")
+        self._submit(file_name, image, self._torch.uint8, save_png)
+
+    def _submit(self, file_name, image, dtype, save) -> None:
         torch = self._torch
         if self._err is not None:
             raise self._err
         src = image.detach()
         ready = torch.cuda.Event()
         ready.record(torch.cuda.current_stream(src.device))
-        host = torch.empty(src.shape, dtype=torch.float32, pin_memory=True)
+        host = torch.empty(src.shape, dtype=dtype, pin_memory=True)
         with torch.cuda.stream(self._stream):
             self._stream.wait_event(ready)
             host.copy_(src, non_blocking=True)
             src.record_stream(self._stream)      # keep the device tensor alive until the copy has run
             done = torch.cuda.Event()
             done.record(self._stream)
-        self._q.put((file_name, host, done))
+        self._q.put((file_name, host, done, save))
 
     def _run(self):
         while True:
@@ -99,15 +122,17 @@ class AsyncRawWriter:
             if item is None:
                 return
             try:
-                file_name, host, done = item
+                file_name, host, done, save = item
                 done.synchronize()
-                save_raw_float32_image(file_name, host.numpy())
+                save(file_name, host.numpy())
             except Exception as e:   # noqa: BLE001 -- surfaced by submit / close
                 self._err = e
 
     def close(self):
-        self._q.put(None)
-        self._thread.join()
+        for _ in self._threads:
+            self._q.put(None)
+        for th in self._threads:
+            th.join()
         if self._err is not None:
             raise self._err
 

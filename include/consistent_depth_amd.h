@@ -229,6 +229,28 @@ int cd_depth_to_points(const float* depths, const float* intrinsics, int N, int 
 int cd_frame_median_scales(const float* inv_src, const float* inv_cmp, int N, int H, int W, float* scales_out, int* n_valid_out,
                            float* scaled_out, void* stream);
 
+/* Colour-mapped previews of inverse depth maps (utils/visualization.py:20-37 visualize_depth, :40-101 visualize_depth_dir).
+ * cd_depth_range: per plane of planes (N,H,W), one workgroup each, count_out[i] and stats_out[i][4]:
+ *   CD_RANGE_MINMAX      count = finite values; stats = min, min, max, max of the finite values (NaN x 4 when there is none);
+ *   CD_RANGE_PERCENTILE  count = finite values; stats = the two order statistics of the finite values that bracket np.percentile's
+ *                        virtual index (count - 1) * q_lo (float32 product, like numpy's for a float32 array), then the two for q_hi;
+ *                        q_lo, q_hi are quantiles in [0, 1].  Exact selection (bitwise np.sort's elements); the caller interpolates;
+ *   CD_RANGE_NANMAX      count = H * W; stats = min, min, max, max over ALL values, NaN if the plane holds a NaN (np.amin / np.amax).
+ * cd_depth_range_fold (one small workgroup): the directory-wide range on the device.  nan_max = 0: dmin = min of stats[i][0],
+ * dmax = max(0, stats[i][3]) over the planes with count > 0 (+inf / 0 when there is none: what float32 makes of the reference's
+ * initial sys.float_info.max / .min).  nan_max = 1: NaN-propagating min of stats[i][0] and max of stats[i][3] over all planes.
+ * cd_depth_colorize: out (N,H,W,3) u8 = table[idx], idx = uint8(sqrt((d - *dmin) / (*dmax - *dmin)) * 255), every step a correctly
+ * rounded float32 operation; idx is the low byte of the int32 truncation, 0 for NaN and for |value| >= 2^31 (the reference on
+ * x86).  dmin, dmax: DEVICE pointers; table: 256 x 3 u8 on the device, R,G,B; bgr != 0 writes B,G,R. */
+#define CD_RANGE_MINMAX 0
+#define CD_RANGE_PERCENTILE 1
+#define CD_RANGE_NANMAX 2
+int cd_depth_range(const float* planes, int N, int H, int W, int mode, float q_lo, float q_hi, int* count_out, float* stats_out,
+                   void* stream);
+int cd_depth_range_fold(const int* counts, const float* stats, int N, int nan_max, float* dmin_out, float* dmax_out, void* stream);
+int cd_depth_colorize(const float* planes, int N, int H, int W, const float* dmin, const float* dmax, const unsigned char* table,
+                      int bgr, unsigned char* out, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Depth CNN layers (reference: the un-vendored Mannequin-Challenge hourglass called at
  * monodepth/mannequin_challenge_model.py:60; architecture SURVEY.md appendix A.3).
