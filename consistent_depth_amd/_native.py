@@ -40,6 +40,7 @@ SIGNATURES = {
     "cd_gather_pairs": (c_i, [c_p, c_p, c_i, c_p, c_p]),
     "cd_sample_bilinear_border": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p]),
     "cd_flow_consistency_masks": (c_i, [c_p, c_p, c_p, c_p, c_i, ctypes.c_double, ctypes.c_double, c_i, c_i, c_i, c_p, c_p, c_p]),
+    "cd_flow_stage_masks": (c_i, [c_p, c_p, c_p, c_i, c_i, ctypes.c_double, ctypes.c_double, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),
     "cd_warp_image": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),
     "cd_depth_to_points": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
     "cd_frame_median_scales": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),

@@ -45,7 +45,8 @@ def hipcc() -> str:
 # Per-file flags.  loss_sweep.hip: the SLP vectorizer pairs the two pixels of a lane into v_pk_*_f32 instructions -- which issue at
 # HALF the rate of their scalar forms on gfx950 (no gain) and need register moves to form the pairs: 80 v_mov per two items in the fast
 # source pass, 412 vector instructions instead of 386 (static census, profiles/loss_sweep_isa_r05.txt).
-EXTRA_FLAGS = {"loss_sweep.hip": ["-fno-slp-vectorize"]}
+# flow_stage.hip: the masks reproduce every fp32 rounding of the reference; the default -ffp-contract=fast fuses a * b + c in the backend.
+EXTRA_FLAGS = {"loss_sweep.hip": ["-fno-slp-vectorize"], "flow_stage.hip": ["-ffp-contract=off"]}
 
 
 def build(force: bool = False, verbose: bool = False) -> str:

@@ -26,6 +26,9 @@ static inline void allow_full_lds() {
     }
 }
 
+// two x-adjacent floats = ONE 8-byte load at a 4-byte-aligned address (the bilinear taps of a row: warp.hip, flow_stage.hip)
+struct __attribute__((packed, aligned(4))) FloatPair { float a, b; };
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);

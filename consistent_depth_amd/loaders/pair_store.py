@@ -21,6 +21,7 @@ into the static input buffers of a captured step graph.
 from __future__ import annotations
 
 import ctypes
+import os
 
 import numpy as np
 import torch
@@ -255,6 +256,49 @@ class PairStore:
     def from_directory(cls, path: str, meta_file: str, device=None):
         """Load the reference's on-disk layout into HBM."""
         return cls(device=device, **cls.load_directory(path, meta_file))
+
+    @classmethod
+    def from_flow_directory(cls, path: str, meta_file: str, frame_pairs, overlap_ratio: float, flow_thresh: float = 1.0,
+                            color_thresh: float = 1.0, device=None):
+        """A store from colours and flows alone: the masks of the reference's flow stage (flow.py:199-228) are computed on the
+        device, as bytes, from the uploaded R,G,B colours summed in the files' B,G,R order (cd_flow_stage_masks with
+        reverse_channels = 1: the reference's bits), and the pairs of `frame_pairs` whose two masks do not both keep
+        `overlap_ratio` of the pixels are dropped by the rule and in the order of `Flow.check_good_flow_pairs`, from the kernel's
+        counts.  No mask PNG and no pair list is read or written; equal to `from_directory` on a clip whose masks and
+        flow_list.json the `Flow` stage wrote from the same arguments."""
+        from . import video_dataset as vd
+        from ..flow import Flow
+        from ..utils import consistency, frame_sampling as sampling
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        color_fmt = os.path.join(path, "color_down", "frame_{:06d}.raw")
+        flow_fmt = os.path.join(path, "flow", "flow_{:06d}_{:06d}.raw")
+        cand = sorted(sampling.SamplePairs.to_one_way([(int(a), int(b)) for a, b in frame_pairs]))
+        if not cand:
+            raise ValueError("from_flow_directory: no frame pairs given")
+        frames = sorted({f for p in cand for f in p})
+        row = {f: r for r, f in enumerate(frames)}
+        color = torch.stack([vd.load_color(color_fmt.format(f)) for f in frames]).to(dev)
+        flows = torch.stack([torch.stack([vd.load_flow(flow_fmt.format(a, b)) for a, b in ((i, j), (j, i))]) for i, j in cand]).to(dev)
+        masks, counts = consistency.flow_stage_masks(
+            flows, color, torch.tensor([[row[i], row[j]] for i, j in cand], dtype=torch.int64, device=dev),
+            flow_thresh, color_thresh, reverse_channels=True)
+        hw = color.shape[2] * color.shape[3]
+        valid = {}
+        for (i, j), c in zip(cand, counts.cpu().tolist()):
+            valid[(i, j)], valid[(j, i)] = c[0], c[1]
+        good = Flow(path, path).good_pairs(frame_pairs, overlap_ratio, ratio=lambda i, j: valid[(i, j)] / hw)
+        if not good:
+            raise Exception("No good frame pairs are found.")
+        pairs = [tuple(p) for p in sampling.SamplePairs.to_one_way(good)]     # read_pair_list's order of the same list
+        keep_frames = sorted({f for p in pairs for f in p})
+        at = {p: n for n, p in enumerate(cand)}
+        sel = torch.tensor([at[p] for p in pairs], dtype=torch.int64, device=dev)
+        fsel = torch.tensor([row[f] for f in keep_frames], dtype=torch.int64, device=dev)
+        new_row = {f: r for r, f in enumerate(keep_frames)}
+        with np.load(meta_file) as meta:
+            intrinsics, extrinsics = meta["intrinsics"][keep_frames], meta["extrinsics"][keep_frames]
+        return cls(color[fsel], flows[sel], masks[sel], intrinsics, extrinsics, [[new_row[i], new_row[j]] for i, j in pairs],
+                   frame_ids=keep_frames, device=dev)
 
     @classmethod
     def synthetic(cls, n_frames: int, H: int, W: int, flow_ops=("hierarchical2",), seed: int = 0, device=None,

@@ -208,6 +208,18 @@ int cd_flow_consistency_masks(const float* flow_fwd, const float* flow_bwd, cons
                               const float* color1, int C, double flow_thresh, double color_thresh, int B, int H,
                               int W, float* mask_fwd, float* mask_bwd, void* stream);
 
+/* The same masks for P pairs of a resident pair store, in its layout, plus the number of valid pixels of every mask -- the
+ * reference's mask_valid_correspondences and the counting of check_good_flow_pairs (flow.py:46-86, :199-228) in one call.
+ * flows (P,2,2,H,W) [pair, direction, (dx,dy)]; color (F,C,H,W); pair_frames (P,2) int64 rows of `color`, on the device (entries
+ * outside [0, F) are clamped, never dereferenced; callers validate them); masks out (P,2,1,H,W) bytes 0 / 1 (4-byte aligned);
+ * counts out (P,2) int32.  Every output byte and count is overwritten; neither buffer needs to be cleared.  reverse_channels = 1
+ * sums the squared colour differences from channel C-1 down to 0: the reference reads B,G,R files and adds in that order, a store
+ * holds R,G,B, and the fp32 sum depends on the order -- with 1 an R,G,B store gives the reference's masks bit for bit; 0 is the
+ * order of cd_flow_consistency_masks.  P <= 65535, H, W >= 2. */
+int cd_flow_stage_masks(const float* flows, const float* color, const int64_t* pair_frames, int C, int reverse_channels,
+                        double flow_thresh, double color_thresh, int P, int F, int H, int W, uint8_t* masks,
+                        int32_t* counts, void* stream);
+
 /* Depth-based warp of frames into each other (offline stages around the hot path: scale_calibration.py:84-120 ->
  * geometry.py:179-227 warping_field / warp_image):  uv_out[i] (2,H,W) = where pixel (x,y) of frame i, lifted with
  * depths[i] and moved through the two poses, lands in frame tgt_ids[i]; warped_out[i] (C,H,W) = images[tgt_ids[i]]
