@@ -505,6 +505,34 @@ def conv2d_wgrad_strided(x, dy, cin_g, cout_g, ks, dw, workspace, groups=1, x_co
     return dw
 
 
+# ---------------------------------------------------------------- stride 1, all groups in one launch (cd_conv2d_*_grouped)
+def conv2d_grouped(x, packed_w, cin_g, cout_g, ks, groups, bias=None, x_coff=0, out=None, y_coff=0, accumulate=False):
+    """out[:, y_coff : y_coff + groups*cout_g] (+)= conv(x[:, x_coff : x_coff + groups*cin_g], stride 1, padding (ks-1)/2) + bias.
+    packed_w: the packs (pack_weights of (cout_g, cin_g, ks)) of all groups side by side -- the forward packs, or the transposed ones
+    with cin_g / cout_g exchanged for the input gradient.  x and out are (N, *, H, W)."""
+    N, x_ctot, H, W = x.shape
+    if out is None:
+        out = torch.empty(N, groups * cout_g, H, W, dtype=torch.float32, device=x.device)
+    rc = _native.lib().cd_conv2d_fwd_grouped(
+        _native.dev_ptr(x, "x"), x_ctot, x_coff, cin_g, _native.dev_ptr(packed_w, "packed_w"), _group_stride(packed_w, groups),
+        _native.dev_ptr(bias, "bias") if bias is not None else None, _native.dev_ptr(out, "out"), out.shape[1], y_coff, cout_g, groups,
+        int(accumulate), N, H, W, ks, _native.stream_ptr(x.device))
+    _native.check(rc, "cd_conv2d_fwd_grouped")
+    return out
+
+
+def conv2d_wgrad_grouped(x, dy, cin_g, cout_g, ks, dw, workspace, groups, x_coff=0, dy_coff=0, accumulate=False):
+    """dw (groups*cout_g, cin_g, ks, ks) (+)= the weight gradient of conv2d_grouped.  workspace: `groups` equal parts of at
+    least wgrad_workspace_floats(cout_g, cin_g, ks) floats."""
+    N, x_ctot, H, W = x.shape
+    rc = _native.lib().cd_conv2d_wgrad_grouped(
+        _native.dev_ptr(x, "x"), x_ctot, x_coff, cin_g, _native.dev_ptr(dy, "dy"), dy.shape[1], dy_coff, cout_g, groups,
+        _native.dev_ptr(dw, "dw"), int(accumulate), _native.dev_ptr(workspace, "workspace"), workspace.numel() // groups, N, H, W, ks,
+        _native.stream_ptr(x.device))
+    _native.check(rc, "cd_conv2d_wgrad_grouped")
+    return dw
+
+
 # ---------------------------------------------------------------- the 7x7 / 2 RGB stem (cd_conv2d_stem_*)
 def stem_enabled() -> bool:
     """CD_AMD_CONV_STEM=0: HipConv2d keeps the stride-1-plus-sub-sampling path for the 7x7 / 2 RGB stem (A/B on one box)."""

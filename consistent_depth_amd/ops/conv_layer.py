@@ -137,17 +137,13 @@ class _HipConvFn(torch.autograd.Function):
             x, s = (C.subsample2(x.contiguous()) if ctx.native_s2 else x[:, :, ::s, ::s]), 1
         x = x.contiguous()
         N, Cin, H, W = x.shape
-        lib, stream = _native.lib(), _native.stream_ptr(x.device)
         pk, _ = layer._packed(weight)
         y = torch.empty(N, Cout, H, W, dtype=torch.float32, device=x.device)
-        bptr = _native.dev_ptr(bias, "bias") if bias is not None else None
         cfg = _dense_cfg(G, ks, Cin, Cout, N, H, W, x.device)
         if cfg is not None:     # dense k x k (the decoder): the launch shape timed once per shape, like the hourglass engine does
             C.conv2d(x, pk[0], Cin, Cout, ks, bias=bias, out=y, cfg=cfg)
         else:
-            rc = lib.cd_conv2d_fwd_grouped(_native.dev_ptr(x, "x"), Cin, 0, cin_g, pk[0].data_ptr(), layer._pack_stride, bptr, y.data_ptr(), Cout, 0,
-                                           cout_g, G, 0, N, H, W, ks, stream)
-            _native.check(rc, "cd_conv2d_fwd_grouped")
+            C.conv2d_grouped(x, layer._arena, cin_g, cout_g, ks, G, bias=bias, out=y)      # (the arena: pk[0] .. pk[G-1] side by side)
         ctx.layer, ctx.hw, ctx.s = layer, (H, W), s
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
@@ -161,7 +157,6 @@ class _HipConvFn(torch.autograd.Function):
         Cout, cin_g, ks, _ = weight.shape
         G, s = layer.groups, ctx.s
         cout_g = Cout // G
-        lib = _native.lib()
         if ctx.native_s2 and ks == 3:
             return _HipConvFn._backward_strided(ctx, dy)
         dyc = dy.contiguous() if ctx.stem else None
@@ -177,10 +172,8 @@ class _HipConvFn(torch.autograd.Function):
             if ctx.stem:
                 C.conv2d_stem_wgrad(x, dyc, dw, layer._stem_workspace(Cout, cin_g, ks, x.device))
                 return
-            ws, ws_stride = layer._wgrad_workspace(cout_g, cin_g, ks, x.device)
-            rc = lib.cd_conv2d_wgrad_grouped(_native.dev_ptr(x, "x"), Cin, 0, cin_g, dyf.data_ptr(), Cout, 0, cout_g, G, dw.data_ptr(), 0,
-                                             ws.data_ptr(), ws_stride, N, H, W, ks, _native.stream_ptr(x.device))
-            _native.check(rc, "cd_conv2d_wgrad_grouped")
+            ws, _ = layer._wgrad_workspace(cout_g, cin_g, ks, x.device)
+            C.conv2d_wgrad_grouped(x, dyf, cin_g, cout_g, ks, dw, ws, G)
 
         def dgrad():
             # (the stem's dx: a transposed pack of the layer's own -- a stem layer is no member of a PackPool)
@@ -190,9 +183,7 @@ class _HipConvFn(torch.autograd.Function):
             if cfg is not None:
                 C.conv2d(dyf, pkT[0], Cout, Cin, ks, out=dx, cfg=cfg)
             else:
-                rc = lib.cd_conv2d_fwd_grouped(dyf.data_ptr(), Cout, 0, cout_g, pkT[0].data_ptr(), layer._pack_strideT, None, dx.data_ptr(), Cin, 0,
-                                               cin_g, G, 0, N, H, W, ks, _native.stream_ptr(x.device))
-                _native.check(rc, "cd_conv2d_fwd_grouped (dgrad)")
+                C.conv2d_grouped(dyf, pkT[0] if ctx.stem else layer._arenaT, cout_g, cin_g, ks, G, out=dx)
             if ctx.full_hw is not None:      # (strided 1x1: the input was sub-sampled first)
                 st = layer.stride[0]
                 if ctx.native_s2:      # the whole plane in one pass: values at even positions, zeros elsewhere

@@ -17,6 +17,10 @@ LAYER_CASES = [  # (Cin, Cout, k, stride, groups, bias, N, H, W)
     (256, 512, 1, 2, 1, False, 2, 16, 24),   # down-sample shortcut
     (256, 128, 3, 1, 1, True, 2, 12, 20),    # decoder, with bias
     (32, 1, 1, 1, 1, True, 2, 12, 20),       # output head
+    (1024, 1024, 3, 1, 32, False, 2, 12, 12),  # the grouped 3x3 of the last two stages: 32 ...
+    (2048, 2048, 3, 1, 32, False, 2, 12, 12),  # ... and 64 channels per group
+    (512, 512, 3, 1, 32, True, 2, 13, 7),    # grouped with bias (the group's slice of the bias vector), odd extent
+    (24, 24, 3, 1, 3, True, 1, 209, 207),    # grouped on the large side of the launch-shape rule (N*H*W > 8*96*56), three groups
 ]
 
 
